@@ -1,20 +1,26 @@
-"""Benchmark: depth maps/s of the cascade forward on MI355X (BASELINE.json metric), ms per stage,
-roofline of the dominant kernel and the CPU baseline — one JSON line on rank 0.
+"""Benchmark: depth maps/s of the cascade forward on MI355X (BASELINE.json metric) — one JSON line on rank 0.
 
-  python bench.py [--gpus N --steps K --warmup W] [--config cfgC] [--batch B] [--no-cpu-baseline]
-                  [--shard depth|rows|gather [--emulate P]] [--no-shard-latency]
+  python bench.py [--gpus N --steps K --warmup W] [--config cfgC] [--batch B] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-parity-path] [--no-shard-latency]]
+                  [--shard depth|rows|gather [--emulate P]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step,
+dtype, config). ``--dump-outputs DIR`` also writes what the last timed step returned (dump_outputs). ``--full`` adds
+everything else to the line, each from runs of its own after the timed steps: ms per stage and the rooflines (a
+one-stream attribution pass), the B=1 latency, the isolated warp kernel, the fp32 parity path, the committed PMC
+summaries, the CPU baseline and, with N > 1, the depth-sharded latency blocks.
 
 Workload (BASELINE.json configs[2]): DTU 1600x1184, 5 views, 3-stage 48/32/8 hypotheses, bf16 storage
 on 1x MI355X; synthetic seeded images/cameras, synthetic weights with calibrated BN statistics
 (no checkpoints or datasets exist offline). One step = one full CascadeMVSNet forward
 (front-end + 3 x (hypotheses, [GeoFeatureFusion], DepthNet)) over one batch per GPU, inputs resident
 in HBM. Multi-GPU: one process per GPU, each processing its own batch (reference views are
-independent units: weak scaling, no collective in the data path); timing = max over ranks. With N > 1 the
-depth-sharded latency mode (damvsnet_amd/sharded.py: one map's cost volumes over all N GPUs) is timed
+independent units: weak scaling, no collective in the data path); timing = max over ranks. With N > 1 and
+``--full`` the depth-sharded latency mode (damvsnet_amd/sharded.py: one map's cost volumes over all N GPUs) is timed
 after the throughput steps and reported as "depth_sharded"; ``--shard`` makes it the measured mode
 (``--emulate P``: P ranks as threads on one GPU, a functional rehearsal, not a speed figure).
 
-Roofline (damvsnet_amd/costmodel.py): HIP events recorded inside damvs_stage_forward
+Roofline (``--full``; damvsnet_amd/costmodel.py): HIP events recorded inside damvs_stage_forward
 (damvs_stage_forward_probed) around the warp, the U-Net and the regression of every stage of the timed
 steps give the in-pipeline kernel-group times; the headline roofline kernel is the stage-2 warp as the
 product runs it. MFMA utilisation of the U-Net / front-end conv kernels comes from the committed
@@ -80,6 +86,32 @@ def make_inputs(B, N, H, W, device=None, seed=0):
         proj = {k: v.to(device) for k, v in proj.items()}
         ins = {k: v.to(device) for k, v in ins.items()}
     return imgs, proj, dv, ins
+
+
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs: upper bound of all array data written
+
+
+def dump_outputs(out, dirname):
+    """Write what a caller of the timed forward receives as ``dirname/<stage>.<key>.npy`` (float32): every tensor of
+    the per-stage dicts (the forward's top-level keys alias stage 3's tensors and are not written twice). The arrays
+    share DUMP_BYTES evenly; one that is larger than its share is written as a fixed sample of its flattened
+    elements, at indices np.random.default_rng(0).integers(0, numel, share), the same for every run and build.
+    Returns {name: [shape of the output, elements written]}."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"%s.%s" % (st, k): v for st, d in sorted(out.items()) if isinstance(d, dict)
+              for k, v in sorted(d.items()) if torch.is_tensor(v)}
+    share = DUMP_BYTES // (4 * max(len(arrays), 1))
+    written = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.random.default_rng(0).integers(0, flat.numel(), share)
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = [list(t.shape), int(a.size)]
+    return written
 
 
 class StageTimer:
@@ -452,6 +484,14 @@ def main():
                          "(bitwise the one-stream result; ms_per_stage / rooflines come from a one-stream pass)")
     ap.add_argument("--dtype", choices=["bf16", "f32"], default=None,
                     help="override the config's compute dtype (cfgC is bf16 in BASELINE.json; f32 = the parity path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and report everything beyond the headline figure: ms per "
+                         "stage and rooflines (one-stream attribution pass), B=1 latency, the isolated warp kernel, the "
+                         "fp32 parity path, the committed PMC summaries, the CPU baseline and (N > 1) the depth-sharded "
+                         "latency blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them returned to DIR/<stage>.<key>.npy "
+                         "(float32; large arrays as a fixed seeded sample, see dump_outputs); rank 0 only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-path", action="store_true",
                     help="bf16 runs: skip the fp32 parity-path block (20 timed steps of the fp32 forward)")
@@ -464,6 +504,8 @@ def main():
     ap.add_argument("--no-shard-latency", action="store_true",
                     help="N > 1: skip the depth-sharded latency block after the throughput steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -511,7 +553,7 @@ def main():
     pp = None
     # DAMVS_BENCH_PARITY_FIRST=1 (A/B of the in-process order): the parity path before the headline steps
     parity_first = os.environ.get("DAMVS_BENCH_PARITY_FIRST", "0") == "1"
-    if parity_first and dtype == torch.bfloat16 and not args.no_parity_path:
+    if args.full and parity_first and dtype == torch.bfloat16 and not args.no_parity_path:
         pp = parity_path(args, nd, device, imgs, proj, dv, ins, world)
     with torch.no_grad():
         for _ in range(args.warmup):
@@ -520,13 +562,49 @@ def main():
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):  # the range status accumulates over the steps and is read once after them
+        for _ in range(args.steps - 1):  # the range status accumulates over the steps and is read once after them
             net(imgs, proj, dv, ins, check_range=False, **stream_kw(args))
+        out = net(imgs, proj, dv, ins, check_range=False, **stream_kw(args))  # the last timed step: --dump-outputs
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         net.DepthNet.check_range()  # raises DamvsRangeError if any timed forward produced non-finite maps
+    from damvsnet_amd.dist import max_over_ranks
+    elapsed = max_over_ranks(elapsed, device=coll_device(device))
+    maps = args.steps * args.batch * world
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    del out
+    head = {
+        "metric": "depth maps/sec (full CascadeMVSNet forward)",
+        "value": round(maps / elapsed, 4),
+        "unit": "depth maps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": dname,
+        "data": "synthetic (seeded DTU-like images/cameras, synthetic weights with calibrated BN stats)",
+        "config": {"workload": "%s: %s" % (args.config, desc), "batch_per_gpu": args.batch,
+                   "frontend": args.frontend,
+                   "global_batch": args.batch * world, "height": H, "width": W, "views": N,
+                   "ndepths": list(nd), "streams": args.streams, "stream_offset": eff_offset(args, dname),
+                   "parallelism": "replicas x%d (reference views sharded over ranks)" % world},
+        "range_status": "ok: every stage of every timed forward finite (damvs_stage_status, read after the steps)",
+    }
+    if dumped is not None:
+        head["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if not args.full:  # a plain run ends here: the headline line and nothing measured beyond it
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
+
+    with torch.no_grad():
         # attribution pass, one stream (per-phase and per-kernel-group times are not separable when sub-batches
         # overlap): HIP events at the phase boundaries and inside damvs_stage_forward_probed
         timer = StageTimer()
@@ -537,9 +615,6 @@ def main():
         torch.cuda.synchronize()
         net.DepthNet.check_range()
         net.DepthNet.probe = None
-    from damvsnet_amd.dist import max_over_ranks
-    elapsed = max_over_ranks(elapsed, device=coll_device(device))
-    maps = args.steps * args.batch * world
     if not parity_first and dtype == torch.bfloat16 and not args.no_parity_path:  # every rank takes part (max over ranks)
         pp = parity_path(args, nd, device, imgs, proj, dv, ins, world)
     phases = {k: round(statistics.mean(v), 3) for k, v in timer.per_phase_ms().items()}
@@ -554,23 +629,7 @@ def main():
         achieved = alg / (pipe_ms * 1e-3) / 1e9
         tr = pmc_traffic(args.config, args.batch, dtype=dname)  # committed PMC profiles of this dtype
         result = {
-            "metric": "depth maps/sec (full CascadeMVSNet forward)",
-            "value": round(maps / elapsed, 4),
-            "unit": "depth maps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": dname,
-            "data": "synthetic (seeded DTU-like images/cameras, synthetic weights with calibrated BN stats)",
-            "config": {"workload": "%s: %s" % (args.config, desc), "batch_per_gpu": args.batch,
-                       "frontend": args.frontend,
-                       "global_batch": args.batch * world, "height": H, "width": W, "views": N,
-                       "ndepths": list(nd), "streams": args.streams, "stream_offset": eff_offset(args, dname),
-                       "parallelism": "replicas x%d (reference views sharded over ranks)" % world},
+            **head,
             "ms_per_stage": phases,
             "latency_b1": lat,
             "roofline": {"kernel": "warp_split_kernel stage2 (fused homography warp + adaptive aggregation, 2 lanes "
@@ -589,7 +648,6 @@ def main():
                          "isolated_ms_per_launch": round(iso_ms, 4),
                          "isolated_frac": round(alg / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "hot_path_roofline": hp,
-            "range_status": "ok: every stage of every timed forward finite (damvs_stage_status, read after the steps)",
             "mfma_utilisation": pmc_mfma(args.config, args.batch, dtype=dname),
         }
         if pp is not None:

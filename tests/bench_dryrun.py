@@ -1,4 +1,5 @@
-"""bench.py's N > 1 path as a CPU gloo job (tests/test_bench_multirank.py launches it under torch.distributed.run).
+"""bench.py's N > 1 path as a CPU gloo job (tests/test_bench_multirank.py launches it under torch.distributed.run
+with --full: the depth-sharded blocks and their guard belong to the full run).
 
 Everything bench.main() does across ranks runs for real -- the process group, the barriers around the timed steps,
 the max-over-ranks timing, rank 0's JSON line, the timer guard around the depth-sharded blocks and the all_reduce

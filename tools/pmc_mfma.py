@@ -60,7 +60,7 @@ def main():
     cmd = ["rocprofv3", "--pmc"] + counters + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "run", "--",
                                                sys.executable, os.path.join(REPO, "bench.py"), "--config", args.config,
                                                "--batch", str(args.batch), "--steps", "2", "--warmup", "1",
-                                               "--dtype", args.dtype, "--no-parity-path",
+                                               "--dtype", args.dtype, "--full", "--no-parity-path",
                                                "--no-cpu-baseline", "--no-shard-latency"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
     if r.returncode != 0:

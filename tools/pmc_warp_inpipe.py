@@ -4,7 +4,7 @@ rate, L1 -> L2 requests and fabric fetch bytes.
 
   python tools/pmc_warp_inpipe.py --out gpurun_out/pmc_inpipe
 
-One `rocprofv3 --pmc ... --kernel-trace` pass per counter group over `bench.py --streams 1 --warmup 1 --steps 2`
+One `rocprofv3 --pmc ... --kernel-trace` pass per counter group over `bench.py --full --streams 1 --warmup 1 --steps 2`
 (the B=4 stage-2 warp runs 1 + 2 times in the steps and 2 times in the attribution pass: 5 in-pipeline launches;
 then bench.py's isolated loop re-launches it on the pipeline's features but with the stage-1-style linear hypotheses
 from depth_values, the same for every pixel, so its gathers are far more coherent than the pipeline's).
@@ -40,7 +40,8 @@ def run_pass(i, counters, out):
     d = os.path.join(out, "p%d" % i)
     cmd = ["rocprofv3", "--pmc"] + counters + ["--kernel-trace", "--output-format", "csv", "-d", d, "-o", "run", "--",
                                               sys.executable, os.path.join(REPO, "bench.py"), "--streams", "1",
-                                              "--warmup", "1", "--steps", "2", "--no-cpu-baseline", "--no-parity-path",
+                                              "--warmup", "1", "--steps", "2", "--full", "--no-cpu-baseline",
+                                              "--no-parity-path",
                                               "--dtype", DTYPE]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
     if r.returncode != 0:

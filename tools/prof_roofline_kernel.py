@@ -1,4 +1,4 @@
-"""Launch segments of the roofline kernel in a rocprofv3 kernel trace of `python bench.py`.
+"""Launch segments of the roofline kernel in a rocprofv3 kernel trace of `python bench.py --full`.
 
 The bench launches the stage-2 warp with three grid sizes: the timed steps run the batch as sub-batches on
 concurrent streams, the attribution pass runs the whole batch on one stream (bench.py's

@@ -2,7 +2,7 @@
 
 Steps are delimited by the regression kernels (one prob_regress / prob_mfma / head launch per stage, 3 per
 forward). Also prints the average of the last `roofline_iters` launches of the roofline kernel
-(bench.py's warp_roofline loop runs last), to check against the bench line's roofline.ms_per_launch."""
+(bench.py --full's warp_roofline loop runs last), to check against the bench line's roofline.ms_per_launch."""
 import collections
 import csv
 import sys
