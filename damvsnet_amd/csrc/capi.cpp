@@ -404,7 +404,7 @@ ConvArgs conv_args(const damvs_stage* st, int li, int B, const Shapes& S, int li
   a.wscale = P.wscale;
   a.nphase = P.nphase;
   std::memcpy(a.ph, P.ph, sizeof(a.ph));
-  if (P.kind == DECONV_S2 && P.wpack_pair && P.cout == 8 && !conv_xpair_disabled()) {
+  if (P.kind == DECONV_S2 && P.wpack_pair && P.cout == 8) {
     a.xpair = 1;
     a.wpack = P.wpack_pair;
     a.nphase = P.nphase_pair;
@@ -553,7 +553,9 @@ int damvs_stage_create(const damvs_costreg_params* cr, const damvs_aggweight_par
         }
     const int kexp = dtype == DAMVS_BF16 ? 0 : split_exponent(wf);
     P.wscale = std::ldexp(1.f, -kexp);
-    if (dtype == DAMVS_BF16) {
+    if (P.kind == DECONV_S2 && P.cout == 8) {
+      // conv11 runs on its x-pair packing alone (wpack_pair below; conv_args): no 8-phase packing
+    } else if (dtype == DAMVS_BF16) {
       std::vector<uint16_t> pk;
       pack_layer<uint16_t>(P, wf, E, pk, cvt_bf16);
       rc = upload(pk.data(), pk.size() * 2, &P.wpack);
@@ -1124,16 +1126,6 @@ void pack_2d_xpair(const damvs_conv2d* L, const float* W, std::vector<S>& out, S
   }
 }
 
-bool conv2d_wide32_disabled() {  // DAMVS_CONV2D_WIDE32=0: fp32 wide layers on the 16-K generic kernels (A/B)
-  const char* v = getenv("DAMVS_CONV2D_WIDE32");
-  return v && v[0] == '0';
-}
-
-bool conv2d_xpair_disabled() {
-  const char* v = getenv("DAMVS_CONV2D_XPAIR");
-  return v && v[0] == '0';
-}
-
 void conv2d_out(const damvs_conv2d* L, int Hi, int Wi, int* Ho, int* Wo) {
   const damvs_conv2d_desc& d = L->d;
   if (d.transposed) {
@@ -1172,7 +1164,7 @@ int damvs_conv2d_create(const damvs_conv2d_desc* desc, const float* weight, cons
   L->MTtot = (d.cout + 15) / 16;
   L->cout_pad = L->MTtot * 16;
   L->cout_store = (d.cout + 3) / 4 * 4;
-  L->xpair = d.transposed && d.stride == 2 && d.cout == 8 && d.ngeo == 0 && d.c0 + d.c1 > 0 && !conv2d_xpair_disabled();
+  L->xpair = d.transposed && d.stride == 2 && d.cout == 8 && d.ngeo == 0 && d.c0 + d.c1 > 0;
   int rc = L->xpair ? build_phases_2d_xpair(L) : build_phases_2d(L);
   if (rc == DAMVS_OK && d.c0 + d.c1 + d.ngeo > 0) {
     if (dtype == DAMVS_BF16) {
@@ -1376,15 +1368,14 @@ int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int
   a.div_wq = make_fastdiv(a.Wq);
   a.div_hq = make_fastdiv(a.Hq);
   std::memcpy(a.ph, L->ph, sizeof(a.ph));
-  if (L->wpack32 && !conv2d_wide32_disabled()) {  // fp32: the 32-K split packing when the wide or halo kernel takes it
-    Conv2dArgs a32 = a;
+  Conv2dArgs a32 = a;
+  if (L->wpack32) {  // fp32: the same layer on its 32-K split packing (same taps, K chunks of 32)
     std::memcpy(a32.ph, L->ph32, sizeof(a32.ph));
     a32.wpack = L->wpack32;
     a32.wide32 = 1;
-    const hipError_t e = launch_conv2d(reinterpret_cast<hipStream_t>(stream), L->dtype, a32);
-    if (e != hipErrorNotSupported) return hip_check(e, "conv2d launch");
   }
-  return hip_check(launch_conv2d(reinterpret_cast<hipStream_t>(stream), L->dtype, a), "conv2d launch");
+  return hip_check(launch_conv2d(reinterpret_cast<hipStream_t>(stream), L->dtype, a, L->wpack32 ? &a32 : nullptr),
+                   "conv2d launch");
 }
 
 }  // extern "C"

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "switches.h"
+
 namespace damvs {
 
 typedef uint16_t bf16_t;  // bf16 storage (upper half of an IEEE f32)
@@ -160,10 +162,11 @@ bool warp_split_for(int bytes, int N);  // the channel-split warp serves NHWC ma
 hipError_t launch_block_channels(hipStream_t s, int store, const FeatPtrs& src, const FeatPtrs& dst, int N, int B,
                                  int hw, int C);
 hipError_t launch_conv3d(hipStream_t s, int store, const ConvArgs& a);
-hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a);
-bool conv2d_wide_shape_ok(const Conv2dArgs& a);
+// a: the layer on its 16-K packing (bf16: its only one); a32: the same fp32 layer on its 32-K split packing (a32->wide32
+// set), or nullptr when it has none. conv2d_route (k_conv2d.hip) picks the kernel and the packing.
+hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a, const Conv2dArgs* a32);
 // layers whose only inputs are fp32 planes (c0 = c1 = 0), on the VALU (k_planes.hip)
-hipError_t launch_conv2d_planes(hipStream_t s, int store, const Conv2dArgs& a);  // the wide kernel takes the layer (given 32-K phase data)
+hipError_t launch_conv2d_planes(hipStream_t s, int store, const Conv2dArgs& a);
 struct BorderArgs {
   float corr[9 * 16];  // [tap][channel] of a 3x3 conv, channels < 16
 };
@@ -192,8 +195,6 @@ struct FusionArgs {
 };
 hipError_t launch_fusion_view(hipStream_t s, const FusionArgs& a);
 
-bool conv_lds_disabled();  // DAMVS_CONV_NO_LDS=1 selects the global-gather conv kernel (A/B testing)
-bool conv_xpair_disabled();  // x-pair deconv phases only with DAMVS_CONV_XPAIR=1
 hipError_t launch_prob_conv(hipStream_t s, int store, int B, int Cb, int D, int h, int w, const void* feat,
                             const float* wprob, const float* prob_init, float* logits);
 hipError_t launch_prob_regress(hipStream_t s, int store, int B, int Cb, int D, int h, int w, const void* feat,
@@ -210,10 +211,23 @@ hipError_t launch_prob_mfma(hipStream_t s, int store, int B, int D, int h, int w
                             float pscale, const float* prob_init, const float* hyps, float* depth, float* conf,
                             float* var, float* prob);
 size_t prob_mfma_smem(int store, int D);
-bool prob_mfma_disabled();  // DAMVS_PROB_MFMA=0 (A/B testing)
 bool prob_mfma_enabled(int store);  // bf16 unless DAMVS_PROB_MFMA=0; fp32 only with DAMVS_PROB_MFMA=1
 hipError_t launch_regress(hipStream_t s, int B, int D, int h, int w, const float* logits, const float* hyps,
                           float* depth, float* conf, float* var, float* prob);
 
+#ifdef __HIPCC__
+// Launch a kernel whose dynamic LDS may exceed the 64 KB a kernel gets without asking: above that, raise the kernel's
+// limit first. Returns the attribute call's error, else the launch's.
+template <typename... P, typename... A>
+hipError_t launch_big_lds(void (*k)(P...), dim3 grid, dim3 block, size_t smem, hipStream_t s, const A&... args) {
+  if (smem > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)smem);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k, grid, block, smem, s, args...);
+  return hipGetLastError();
+}
+#endif
 
 }  // namespace damvs

@@ -21,9 +21,6 @@ namespace {
 
 template <typename T> using Frag2 = MmaFrag<T>;
 
-template <typename T> struct T_is_bf16 { static constexpr bool value = false; };
-template <> struct T_is_bf16<bf16_t> { static constexpr bool value = true; };
-
 constexpr int kG2 = 4;  // 16-pixel groups per wave
 
 template <typename T> __device__ __forceinline__ typename Frag2<T>::raw pack_vals(const float* v);
@@ -1075,32 +1072,32 @@ hipError_t launch_halo_t(hipStream_t s, const Conv2dArgs& a, int dmin, int span)
   const long long nblk = (long long)tx * ty * a.B * a.nphase;
   const dim3 grid((unsigned)nblk, (unsigned)(a.MTtot / (MT * WM)));
   auto k = a.c1 > 0 ? conv2d_halo_kernel<T, MT, WM, true, W32, RS> : conv2d_halo_kernel<T, MT, WM, false, W32, RS>;
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, grid, dim3(256), smem, s, a, tx, ty, nsl, dmin, span);
-  return hipGetLastError();
+  return launch_big_lds(k, grid, dim3(256), smem, s, a, tx, ty, nsl, dmin, span);
 }
 
-// Returns hipErrorNotSupported when the halo kernel does not take the layer. W32: the fp32 layer's 32-K split form.
-template <typename T, bool W32 = false>
-hipError_t launch_halo(hipStream_t s, const Conv2dArgs& a, bool dry = false) {
-  constexpr int KC = W32 ? 32 : 4 * Stor<T>::E;
+// The kernel conv2d_route picked for a layer (the families are described at their kernels), and what its launcher needs.
+enum class Conv2dFamily { invalid, planes, xpair_lds, xpair_gather, lds3, lds_s2, halo, wide, gather, gather32 };
+struct Conv2dRoute {
+  Conv2dFamily family;
+  bool k32;        // the layer runs on its 32-K split packing (fp32: halo, wide, gather32), else on the 16-K one
+  int mt;          // halo, gather, gather32: cout tiles a wave
+  int wm;          // halo: cout-tile rows of the wave grid; wide: 1 = the 64-channel block, 2 = the 128-channel block
+  bool rs;         // halo (32-K), wide (fp32): the rolling loop
+  bool r1;         // wide (fp32, input stride 2): one-row tiles
+  int dmin, span;  // halo, wide: the range of the tap offsets
+};
+
+// Whether the halo kernel takes the layer, and its cout tile (r.mt, r.wm, r.rs, r.dmin, r.span). KC: K per chunk of
+// the packing; w32: the fp32 layer's 32-K split form (the narrow layers, cout <= 32).
+bool halo_route(const Conv2dArgs& a, int KC, bool w32, bool bf16, Conv2dRoute& r) {
   // largest cout tile count (MTtot) the halo kernel takes: its B reuse pays off for narrow outputs,
   // while wide outputs are bound by the A (weight) stream the gather kernel already amortises
   constexpr int max_mt = 2;  // (8: the wide layers too, measured 192-194 against 203-204 maps/s in round 3)
   // one-slice inputs (Cin = KC) and single cout tiles as well: the half-resolution GeoBlock convs with a depth
-  // plane (32+g -> 32: 173 -> 146 us, 32+g -> 16: 101 -> 79 us at B=4); DAMVS_CONV2D_HALO_THIN=0 restores the
-  // gather kernel for them
-  static const bool thin = [] {
-    const char* v = getenv("DAMVS_CONV2D_HALO_THIN");
-    return !(v && v[0] == '0');
-  }();
+  // plane (32+g -> 32: 173 -> 146 us, 32+g -> 16: 101 -> 79 us at B=4 against the gather kernel)
   if (a.MTtot > max_mt || (a.MTtot > 2 && a.MTtot < 8) || a.in_stride != 1 || a.c0 % KC || a.c1 % KC ||
-      a.c0 + a.c1 < (thin ? KC : 2 * KC) || a.MTtot < (thin ? 1 : 2) || a.ngeo > 1)
-    return hipErrorNotSupported;
+      a.c0 + a.c1 < KC || a.MTtot < 1 || a.ngeo > 1)
+    return false;
   int dmin = 0, dmax = 0;
   for (int p = 0; p < a.nphase; ++p)
     for (int t = 0; t < a.ph[p].ntaps; ++t)
@@ -1109,26 +1106,37 @@ hipError_t launch_halo(hipStream_t s, const Conv2dArgs& a, bool dry = false) {
         dmax = a.ph[p].tap[t][d] > dmax ? a.ph[p].tap[t][d] : dmax;
       }
   const int span = dmax - dmin + 1;
-  if ((HGR + span - 1) * (HGC + span - 1) > 512) return hipErrorNotSupported;  // PER = 8 fill pieces a thread
+  if ((HGR + span - 1) * (HGC + span - 1) > 512) return false;  // PER = 8 fill pieces a thread
+  r.dmin = dmin;
+  r.span = span;
+  r.wm = 1;
+  r.rs = w32 && switch_on(SW_HALO_RS);  // the rolling tap loop unless DAMVS_HALO_RS=0 (read per call: the bitwise test flips it)
   // cout tile as wide as keeps about one wave per SIMD busy (the tile count is small for these layers)
   const long long tiles = (long long)((a.Wq + HGC - 1) / HGC) * ((a.Hq + HGR - 1) / HGR) * a.B * a.nphase;
-  if (dry) return (a.MTtot >= 8 ? a.MTtot % 8 == 0 : (W32 ? a.MTtot <= 2 : true)) ? hipSuccess : hipErrorNotSupported;
-  if constexpr (W32) {  // fp32 32-K form: the narrow layers (cout <= 32); the rolling tap loop unless DAMVS_HALO_RS=0
-    const char* rv = getenv("DAMVS_HALO_RS");  // (read per call: the bitwise test flips it)
-    const bool rs = !(rv && rv[0] == '0');
-    if (a.MTtot == 2) return rs ? launch_halo_t<T, 2, 1, true, true>(s, a, dmin, span) : launch_halo_t<T, 2, 1, true>(s, a, dmin, span);
-    if (a.MTtot == 1) return rs ? launch_halo_t<T, 1, 1, true, true>(s, a, dmin, span) : launch_halo_t<T, 1, 1, true>(s, a, dmin, span);
-    return hipErrorNotSupported;
+  if (w32) r.mt = a.MTtot <= 2 ? a.MTtot : 0;
+  else if (a.MTtot >= 8) r.mt = a.MTtot % 8 == 0 ? 4 : 0, r.wm = 2;  // wide: 2 x 2 wave grid, 4 cout tiles x 128 pixels a wave
+  else if (bf16 && a.MTtot % 8 == 0 && tiles * (a.MTtot / 8) >= 240) r.mt = 8;
+  else if (a.MTtot % 4 == 0 && tiles * (a.MTtot / 4) >= 240) r.mt = 4;
+  else if (a.MTtot % 2 == 0) r.mt = 2;
+  else r.mt = a.MTtot == 1 ? 1 : 0;
+  return r.mt != 0;
+}
+
+template <typename T>
+hipError_t launch_halo(hipStream_t s, const Conv2dArgs& a, const Conv2dRoute& r) {
+  if constexpr (sizeof(T) == 4) {
+    if (r.k32) {
+      if (r.mt == 2) return r.rs ? launch_halo_t<T, 2, 1, true, true>(s, a, r.dmin, r.span) : launch_halo_t<T, 2, 1, true>(s, a, r.dmin, r.span);
+      return r.rs ? launch_halo_t<T, 1, 1, true, true>(s, a, r.dmin, r.span) : launch_halo_t<T, 1, 1, true>(s, a, r.dmin, r.span);
+    }
   }
-  if (a.MTtot >= 8) {  // wide: 2 x 2 wave grid, 4 cout tiles x 128 pixels a wave
-    if (a.MTtot % 8 == 0) return launch_halo_t<T, 4, 2>(s, a, dmin, span);
-    return hipErrorNotSupported;
+  if (r.wm == 2) return launch_halo_t<T, 4, 2>(s, a, r.dmin, r.span);
+  switch (r.mt) {
+    case 8: return launch_halo_t<T, 8, 1>(s, a, r.dmin, r.span);
+    case 4: return launch_halo_t<T, 4, 1>(s, a, r.dmin, r.span);
+    case 2: return launch_halo_t<T, 2, 1>(s, a, r.dmin, r.span);
+    default: return launch_halo_t<T, 1, 1>(s, a, r.dmin, r.span);
   }
-  if (T_is_bf16<T>::value && a.MTtot % 8 == 0 && tiles * (a.MTtot / 8) >= 240) return launch_halo_t<T, 8, 1>(s, a, dmin, span);
-  if (a.MTtot % 4 == 0 && tiles * (a.MTtot / 4) >= 240) return launch_halo_t<T, 4, 1>(s, a, dmin, span);
-  if (a.MTtot % 2 == 0) return launch_halo_t<T, 2, 1>(s, a, dmin, span);
-  if (a.MTtot == 1) return launch_halo_t<T, 1, 1>(s, a, dmin, span);
-  return hipErrorNotSupported;
 }
 
 // Wide-layer implicit GEMM (bf16; 128-channel cout blocks; Cin slices of 32; in_stride 1): the stride-1
@@ -1805,47 +1813,46 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? (IS == 1 || R1 ? 
   }
 }
 
-template <typename T, int IS, int WM, bool RS = false, bool R1 = false>
-hipError_t launch_wide_t(hipStream_t s, const Conv2dArgs& a, int dmin, int span) {
+// One form of the wide kernel: conv2d_wide_kernel's template arguments after T and TWO
+template <int IS_, int WM_, bool RS_ = false, bool R1_ = false>
+struct WideTag {
+  static constexpr int IS = IS_, WM = WM_, WRT = R1_ ? 1 : WM_ == 1 && IS_ == 2 ? 2 : 4 / WM_;  // WRT: q-tile rows
+  static constexpr bool RS = RS_, R1 = R1_;
+};
+
+// Dynamic LDS of a wide-kernel form for taps spanning `span` pixels; 0 when the form does not take them
+template <typename T, typename W>
+size_t wide_smem(W, int span) {
   constexpr bool SP = sizeof(T) == 4;
-  constexpr int WRT = R1 ? 1 : WM == 1 && IS == 2 ? 2 : 4 / WM, AR = WM * 256 * WideForm<T>::PL, SLOTS = WideForm<T>::SLOTS;
-  const WideHalo<IS, WRT> hg(span);
-  constexpr int NHB = IS == 1 && !(SP && WM == 1) ? 2 : 1, WPER = RS ? 5 : IS == 1 || R1 ? 7 : 11;
-  constexpr bool AG = SP || !(WM == 1 && IS == 2);  // A fragments from L1 / L2, no A buffers in LDS (the kernel's AG)
-  if (hg.hp * 4 > WPER * 256) return hipErrorNotSupported;
+  constexpr int AR = W::WM * 256 * WideForm<T>::PL, SLOTS = WideForm<T>::SLOTS;
+  const WideHalo<W::IS, W::WRT> hg(span);
+  constexpr int NHB = W::IS == 1 && !(SP && W::WM == 1) ? 2 : 1, WPER = W::RS ? 5 : W::IS == 1 || W::R1 ? 7 : 11;
+  constexpr bool AG = SP || !(W::WM == 1 && W::IS == 2);  // A fragments from L1 / L2, no A buffers in LDS (the kernel's AG)
+  if (hg.hp * 4 > WPER * 256) return 0;
   size_t below_plane = (AG ? 0 : 2 * (size_t)AR * 16) + NHB * (size_t)hg.hp * SLOTS * 16;
   if (!SP && AG && below_plane < 4 * 32 * 68 * 4) below_plane = 4 * 32 * 68 * 4;  // as gofs in the kernel
-  if (below_plane < 4 * 32 * 68 * 4) return hipErrorNotSupported;  // the epilogue's staging tiles stay below the plane halo
-  const int tx = (a.Wq + WC - 1) / WC, ty = (a.Hq + WRT - 1) / WRT;
-  const int nsl = (a.c0 + a.c1) / 32;
-  const size_t smem = below_plane + (size_t)hg.hp * 4 + (RS ? 16 + SLOTS * 16 : 0);  // A chunks, halo slices, plane
-                                                                                    // halo (RS: spare piece slots)
-  if (smem > 160 * 1024) return hipErrorNotSupported;
-  const long long nblk = (long long)tx * ty * a.B * a.nphase;
-  const dim3 grid((unsigned)nblk, (unsigned)(a.MTtot / (4 * WM)));
-  auto k = a.c1 > 0 ? conv2d_wide_kernel<T, true, IS, WM, RS, R1> : conv2d_wide_kernel<T, false, IS, WM, RS, R1>;
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, grid, dim3(256), smem, s, a, tx, ty, nsl, dmin, span);
-  return hipGetLastError();
+  if (below_plane < 4 * 32 * 68 * 4) return 0;  // the epilogue's staging tiles stay below the plane halo
+  const size_t smem = below_plane + (size_t)hg.hp * 4 + (W::RS ? 16 + SLOTS * 16 : 0);  // A chunks, halo slices, plane
+                                                                                       // halo (RS: spare piece slots)
+  return smem > 160 * 1024 ? 0 : smem;
 }
 
-// Shape checks of the wide kernel (K chunks of 32: bf16 packing, or the fp32 layer's 32-K split packing); returns
+template <typename T, typename W>
+hipError_t launch_wide_t(hipStream_t s, const Conv2dArgs& a, W w, int dmin, int span) {
+  const int tx = (a.Wq + WC - 1) / WC, ty = (a.Hq + W::WRT - 1) / W::WRT;
+  const int nsl = (a.c0 + a.c1) / 32;
+  const long long nblk = (long long)tx * ty * a.B * a.nphase;
+  const dim3 grid((unsigned)nblk, (unsigned)(a.MTtot / (4 * W::WM)));
+  auto k = a.c1 > 0 ? conv2d_wide_kernel<T, true, W::IS, W::WM, W::RS, W::R1> : conv2d_wide_kernel<T, false, W::IS, W::WM, W::RS, W::R1>;
+  return launch_big_lds(k, grid, dim3(256), wide_smem<T>(w, span), s, a, tx, ty, nsl, dmin, span);
+}
+
+// Shape checks of the wide kernel (K chunks of 32: bf16 packing, or the fp32 layer's 32-K split packing): input stride
+// 1, or 2 for one phase (the stride-2 GeoBlock convs); cout in 128-channel blocks, or 64 (the 64-channel block). Returns
 // the tap offset range in dmin / span.
 bool wide_shape_ok(const Conv2dArgs& a, int& dmin, int& span) {
-  static const bool s2 = [] {
-    const char* v = getenv("DAMVS_CONV2D_WIDE_S2");
-    return !(v && v[0] == '0');
-  }();
-  static const bool w64 = [] {
-    const char* v = getenv("DAMVS_CONV2D_WIDE64");
-    return !(v && v[0] == '0');
-  }();
-  const bool stride_ok = a.in_stride == 1 || (a.in_stride == 2 && s2 && a.nphase == 1 && a.out_stride == 1);
-  const bool half = w64 && a.MTtot == 4;  // 64 output channels
+  const bool stride_ok = a.in_stride == 1 || (a.in_stride == 2 && a.nphase == 1 && a.out_stride == 1);
+  const bool half = a.MTtot == 4;  // 64 output channels
   if (!stride_ok || a.xpair || a.ngeo > 1 || (a.MTtot % 8 && !half) || a.c0 % 32 || a.c1 % 32 || a.c0 + a.c1 < 64 ||
       a.cout % 32)  // the epilogue finishes whole 32-channel halves per lane
     return false;
@@ -1863,44 +1870,45 @@ bool wide_shape_ok(const Conv2dArgs& a, int& dmin, int& span) {
   return true;
 }
 
-// Returns hipErrorNotSupported when the wide kernel does not take the layer. Input stride 2 (the stride-2 GeoBlock
-// convs, one phase) unless DAMVS_CONV2D_WIDE_S2=0; cout 64 at input stride 1 on the 64-channel block (WM = 1) unless
-// DAMVS_CONV2D_WIDE64=0. T = float: `a` carries the layer's 32-K split packing (a.wide32, damvs_conv2d_forward).
-template <typename T>
-hipError_t launch_wide(hipStream_t s, const Conv2dArgs& a) {
-  static const bool off = [] {
-    const char* v = getenv("DAMVS_CONV2D_WIDE");
-    return v && v[0] == '0';
-  }();
+// Calls f with the WideTag of the wide-kernel form route r names (SP: fp32, which alone has the RS and R1 forms).
+template <bool SP, typename F>
+auto with_wide_form(int in_stride, const Conv2dRoute& r, F f) {
+  if (r.wm == 1) return in_stride == 1 ? f(WideTag<1, 1>()) : f(WideTag<2, 1>());
+  if constexpr (SP) {
+    if (r.rs) return f(WideTag<1, 2, true>());
+    if (r.r1) return f(WideTag<2, 2, false, true>());
+  }
+  return in_stride == 1 ? f(WideTag<1, 2>()) : f(WideTag<2, 2>());
+}
+
+// Whether the wide kernel takes the layer, and in which form (r.wm, r.rs, r.r1, r.dmin, r.span). f32: `a` carries the
+// layer's 32-K split packing (a.wide32, damvs_conv2d_forward).
+bool wide_route(const Conv2dArgs& a, bool f32, Conv2dRoute& r) {
+  if (!wide_shape_ok(a, r.dmin, r.span)) return false;
+  r.wm = a.MTtot % 8 ? 1 : 2;
+  // fp32 64-channel block at input stride 2 (32-column waves, one block per CU): the 32-K gather kernel is faster
+  // (kbench2d H 91.6 -> 63.5 us, profiles/r06/ab_wide_s2r1_r06x/)
+  if (r.wm == 1 && f32 && a.in_stride == 2) return false;
   // fp32 rolling K loop (conv2d_wide_kernel RS) for the stride-1 128-channel block when its halo fits 5 pieces a thread
   // (taps spanning <= 3 pixels); DAMVS_WIDE_RS=0 keeps the AG loop (read per call: the bitwise test flips it)
-  const char* rsv = getenv("DAMVS_WIDE_RS");
-  const bool rs_off = rsv && rsv[0] == '0';
-  int dmin = 0, span = 0;
-  if (off || !wide_shape_ok(a, dmin, span)) return hipErrorNotSupported;
-  if (a.MTtot % 8) {
-    // fp32 64-channel block at input stride 2 (32-column waves, one block per CU): the 32-K gather kernel is faster
-    // (kbench2d H 91.6 -> 63.5 us, profiles/r06/ab_wide_s2r1_r06x/)
-    if (sizeof(T) == 4 && a.in_stride == 2) return hipErrorNotSupported;
-    return a.in_stride == 1 ? launch_wide_t<T, 1, 1>(s, a, dmin, span) : launch_wide_t<T, 2, 1>(s, a, dmin, span);
-  }
-  if constexpr (sizeof(T) == 4) {
-    if (a.in_stride == 1 && span <= 3 && !rs_off) return launch_wide_t<T, 1, 2, true>(s, a, dmin, span);
-  }
-  if constexpr (sizeof(T) == 4) {
-    // the fp32 stride-2 128-channel block on one-row tiles (two blocks per CU): kbench2d E 120 -> 103 us, parity path
-    // 103.0 -> 103.2-103.6 maps/s (profiles/r06/ab_wide_s2r1_r06x/); DAMVS_WIDE_S2R1=0 (read per call) keeps 2-row tiles
-    const char* r1 = getenv("DAMVS_WIDE_S2R1");
-    if (a.in_stride == 2 && !(r1 && r1[0] == '0')) return launch_wide_t<T, 2, 2, false, true>(s, a, dmin, span);
-  }
-  return a.in_stride == 1 ? launch_wide_t<T, 1, 2>(s, a, dmin, span) : launch_wide_t<T, 2, 2>(s, a, dmin, span);
+  r.rs = f32 && r.wm == 2 && a.in_stride == 1 && r.span <= 3 && switch_on(SW_WIDE_RS);
+  // the fp32 stride-2 128-channel block on one-row tiles (two blocks per CU): kbench2d E 120 -> 103 us, parity path
+  // 103.0 -> 103.2-103.6 maps/s (profiles/r06/ab_wide_s2r1_r06x/); DAMVS_WIDE_S2R1=0 (read per call) keeps 2-row tiles
+  r.r1 = f32 && r.wm == 2 && a.in_stride == 2 && switch_on(SW_WIDE_S2R1);
+  const int span = r.span;
+  return 0 != (f32 ? with_wide_form<true>(a.in_stride, r, [span](auto w) { return wide_smem<float>(w, span); })
+                   : with_wide_form<false>(a.in_stride, r, [span](auto w) { return wide_smem<bf16_t>(w, span); }));
+}
+
+template <typename T>
+hipError_t launch_wide(hipStream_t s, const Conv2dArgs& a, const Conv2dRoute& r) {
+  return with_wide_form<sizeof(T) == 4>(a.in_stride, r, [&](auto w) { return launch_wide_t<T>(s, a, w, r.dmin, r.span); });
 }
 
 // conv2d_xpair_lds_kernel's layers: x-pair phases of a 16-channel single-input transposed stride-2 conv whose taps
 // all lie in -1 .. 1 (DAMVS_CONV2D_XPAIR_LDS=0, read per call: the XP gather kernel)
 bool xpair_lds_ok(const Conv2dArgs& a, int KC) {
-  const char* v = getenv("DAMVS_CONV2D_XPAIR_LDS");
-  if ((v && v[0] == '0') || a.c0 != 16 || a.c1 != 0 || a.in_stride != 1 || a.out_stride != 2 || a.Hq != a.Hi ||
+  if (!switch_on(SW_CONV2D_XPAIR_LDS) || a.c0 != 16 || a.c1 != 0 || a.in_stride != 1 || a.out_stride != 2 || a.Hq != a.Hi ||
       a.Wq != a.Wi)
     return false;
   for (int p = 0; p < 2; ++p) {
@@ -1917,8 +1925,7 @@ bool xpair_lds_ok(const Conv2dArgs& a, int KC) {
 bool lds3_ok(const Conv2dArgs& a) {
   // at most one plane, next to at most 16 channels (the layers the gather kernel ran; 32+g goes to the halo kernel);
   // DAMVS_CONV2D_LDS_PLANE=0 (read per call): planes stay on the gather kernel
-  const char* pv = getenv("DAMVS_CONV2D_LDS_PLANE");
-  const int maxg = (pv && pv[0] == '0') || a.c0 > 16 ? 0 : 1;
+  const int maxg = !switch_on(SW_CONV2D_LDS_PLANE) || a.c0 > 16 ? 0 : 1;
   if (a.nphase != 1 || a.out_stride != 1 || a.in_stride != 1 || a.ph[0].ntaps != 9 || a.ngeo > maxg || a.c1 != 0 ||
       a.Ho != a.Hi || a.Wo != a.Wi || (a.ngeo && a.ph[0].gchunks != 1))
     return false;
@@ -1935,26 +1942,22 @@ hipError_t launch_lds2_t(hipStream_t s, const Conv2dArgs& a) {
   return hipGetLastError();
 }
 
-// Returns hipErrorNotSupported when the LDS variant does not take the layer.
-template <typename T>
-hipError_t launch_lds2(hipStream_t s, const Conv2dArgs& a, bool dry = false) {
-  static const bool off = [] {
-    const char* v = getenv("DAMVS_CONV2D_NO_LDS");
-    return v && v[0] == '1';
-  }();
+// Whether the 3x3 LDS-tiled kernel takes the layer: CIN 8 / 16 (bf16: 32 too), cout <= 32 (LDS <= 42 KB).
+bool lds3_route(const Conv2dArgs& a, bool f32) {
   // fp32 layers with a plane stay on the 32-K gather kernel (kbench J 27.8 against 31.2 us on the 16-K LDS form; bench
   // flat, profiles/r06/ab_lds_plane)
-  if (off || !lds3_ok(a) || a.MTtot > 2 || (sizeof(T) == 4 && (a.c0 > 16 || a.ngeo))) return hipErrorNotSupported;  // LDS <= 42 KB
-  if (dry) return a.c0 == 8 || a.c0 == 16 || (sizeof(T) == 2 && a.c0 == 32) ? hipSuccess : hipErrorNotSupported;
+  if (!lds3_ok(a) || a.MTtot > 2 || (f32 && (a.c0 > 16 || a.ngeo))) return false;
+  return a.c0 == 8 || a.c0 == 16 || (!f32 && a.c0 == 32);
+}
+
+template <typename T>
+hipError_t launch_lds3(hipStream_t s, const Conv2dArgs& a) {
   const int MT = a.MTtot;
-  switch (a.c0) {
-    case 8: return MT == 1 ? launch_lds2_t<T, 8, 1>(s, a) : launch_lds2_t<T, 8, 2>(s, a);
-    case 16: return MT == 1 ? launch_lds2_t<T, 16, 1>(s, a) : launch_lds2_t<T, 16, 2>(s, a);
-    case 32:
-      if constexpr (sizeof(T) == 2) return MT == 1 ? launch_lds2_t<T, 32, 1>(s, a) : launch_lds2_t<T, 32, 2>(s, a);
-      return hipErrorNotSupported;
-    default: return hipErrorNotSupported;
+  if constexpr (sizeof(T) == 2) {
+    if (a.c0 == 32) return MT == 1 ? launch_lds2_t<T, 32, 1>(s, a) : launch_lds2_t<T, 32, 2>(s, a);
   }
+  if (a.c0 == 8) return MT == 1 ? launch_lds2_t<T, 8, 1>(s, a) : launch_lds2_t<T, 8, 2>(s, a);
+  return MT == 1 ? launch_lds2_t<T, 16, 1>(s, a) : launch_lds2_t<T, 16, 2>(s, a);
 }
 
 
@@ -1976,14 +1979,12 @@ hipError_t launch_lds_s2_t(hipStream_t s, const Conv2dArgs& a) {
   return hipGetLastError();
 }
 
-// Returns hipErrorNotSupported when the stride-2 LDS variant does not take the layer (CIN 8 / 16, cout <= 32);
-// DAMVS_CONV2D_LDS_S2=0 (read per call) leaves those layers to the gather kernel. Tile rows: 4 (LDS <= 47 KB), 2 for
-// fp32 CIN 16 (59 KB).
+// Whether the stride-2 LDS variant takes the layer (CIN 8 / 16, cout <= 32).
+bool lds_s2_route(const Conv2dArgs& a) { return lds_s2_ok(a) && a.MTtot <= 2 && (a.c0 == 8 || a.c0 == 16); }
+
+// Tile rows: 4 (LDS <= 47 KB), 2 for fp32 CIN 16 (59 KB).
 template <typename T>
-hipError_t launch_lds_s2(hipStream_t s, const Conv2dArgs& a, bool dry = false) {
-  const char* v = getenv("DAMVS_CONV2D_LDS_S2");
-  if ((v && v[0] == '0') || !lds_s2_ok(a) || a.MTtot > 2 || (a.c0 != 8 && a.c0 != 16)) return hipErrorNotSupported;
-  if (dry) return hipSuccess;
+hipError_t launch_lds_s2(hipStream_t s, const Conv2dArgs& a) {
   const bool m2 = a.MTtot == 2;
   constexpr bool SP = sizeof(T) == 4;
   if (a.c0 == 8) return m2 ? launch_lds_s2_t<T, 8, 2, 4>(s, a) : launch_lds_s2_t<T, 8, 1, 4>(s, a);
@@ -2016,83 +2017,91 @@ int gather_mt(const Conv2dArgs& a, bool bf16) {
 
 // fp32 32-K gather form (conv2d_mfma_kernel K32) for the layers with a 32-K packing that neither the wide nor the halo
 // kernel takes; DAMVS_CONV2D_G32=0 (read per call: the parity test flips it) returns them to the 16-K form.
-template <typename T>
-hipError_t launch_gather32(hipStream_t s, const Conv2dArgs& a) {
-  const char* v = getenv("DAMVS_CONV2D_G32");
-  if ((v && v[0] == '0') || a.xpair || a.c0 % 8 || a.c1 % 8 || a.ngeo > 1) return hipErrorNotSupported;
-  switch (gather_mt(a, false)) {
-    case 4: return launch_mt<T, 4, true>(s, a);
-    case 2: return launch_mt<T, 2, true>(s, a);
-    default: return launch_mt<T, 1, true>(s, a);
-  }
+bool gather32_ok(const Conv2dArgs& a) {
+  return switch_on(SW_CONV2D_G32) && !a.xpair && a.c0 % 8 == 0 && a.c1 % 8 == 0 && a.ngeo <= 1;
 }
 
-
-template <typename T>
-hipError_t launch_t(hipStream_t s, const Conv2dArgs& a) {
+// The kernel that runs a layer, decided once and without a HIP call. a: the layer on its 16-K packing (bf16: its only
+// one); a32: the same fp32 layer on its 32-K split packing, or nullptr. Both carry the same taps, so a predicate on
+// shapes and taps answers for both; the K-chunk counts are read from the packing the kernel in question runs on.
+// family invalid: no kernel takes these arguments (hipErrorInvalidValue).
+Conv2dRoute conv2d_route(const Conv2dArgs& a, const Conv2dArgs* a32, int store) {
+  const bool f32 = store == ST_F32;
+  const int KC = f32 ? 16 : 32;  // K per chunk of the 16-K packing (4 * Stor<T>::E)
+  Conv2dRoute r = {};
+  auto is = [&r](Conv2dFamily f) {
+    r.family = f;
+    return r;
+  };
   // 32-bit indices / buffer offsets: every operand must stay below 2 GiB
-  const long long lim = 1LL << 31, es = sizeof(T);
+  const long long lim = 1LL << 31, es = f32 ? 4 : 2;
   const long long npix = (long long)a.B * a.Hi * a.Wi, nout = (long long)a.B * a.Ho * a.Wo * a.cout;
   if (npix * (a.c0 > a.c1 ? a.c0 : a.c1) * es >= lim || nout * es >= lim || (long long)a.B * a.Hq * a.Wq >= lim)
-    return hipErrorInvalidValue;
+    return is(Conv2dFamily::invalid);
   for (int g = 0; g < a.ngeo; ++g)
-    if (((long long)(a.B - 1) * a.geo_bstride[g] + npix / a.B) * 4 >= lim) return hipErrorInvalidValue;
-  if (a.c0 + a.c1 == 0) return launch_conv2d_planes(s, sizeof(T) == 2 ? ST_BF16 : ST_F32, a);  // k_planes.hip
-  if (a.ngeo > 1) return hipErrorInvalidValue;  // the MFMA path takes at most one plane
-  if (a.wide32) {  // fp32 layer with its 32-K split packing: the wide kernel, else the narrow halo kernel, else (unless
-                   // the thin-layer LDS kernel takes it on the 16-K packing) the 32-K gather kernel, else
-                   // hipErrorNotSupported (damvs_conv2d_forward then runs the 16-K packing)
-    if constexpr (sizeof(T) == 4) {
-      hipError_t e = launch_wide<T>(s, a);
-      if (e != hipErrorNotSupported) return e;
-      if (a.c0 % 32 == 0 && a.c1 % 32 == 0) {
-        e = launch_halo<T, true>(s, a);
-        if (e != hipErrorNotSupported) return e;
-      }
-      // the layers the 16-K route gives to the LDS-tiled kernels stay there (thin 3x3 layers, 16-channel slices)
-      if (launch_lds2<T>(s, a, true) == hipSuccess || launch_lds_s2<T>(s, a, true) == hipSuccess ||
-          launch_halo<T>(s, a, true) == hipSuccess)
-        return hipErrorNotSupported;
-      return launch_gather32<T>(s, a);
-    }
-    return hipErrorInvalidValue;
-  }
+    if (((long long)(a.B - 1) * a.geo_bstride[g] + npix / a.B) * 4 >= lim) return is(Conv2dFamily::invalid);
+  if (a.c0 + a.c1 == 0) return is(Conv2dFamily::planes);  // k_planes.hip
+  if (a.ngeo > 1 || (a32 && !f32)) return is(Conv2dFamily::invalid);  // the MFMA path takes at most one plane
   if (a.xpair) {  // x-pair phases (built at layer creation): the LDS x-pair kernel where it fits, else the XP gather kernel
-    if (a.cout != 8 || a.MTtot != 1 || a.ngeo != 0 || a.nphase != 2) return hipErrorInvalidValue;
-    if (xpair_lds_ok(a, 4 * Stor<T>::E)) {
+    if (a.cout != 8 || a.MTtot != 1 || a.ngeo != 0 || a.nphase != 2) return is(Conv2dFamily::invalid);
+    return is(xpair_lds_ok(a, KC) ? Conv2dFamily::xpair_lds : Conv2dFamily::xpair_gather);
+  }
+  if (a32) {  // fp32 layer with a 32-K split packing: the wide kernel, else the narrow halo kernel
+    r.k32 = true;
+    if (wide_route(*a32, true, r)) return is(Conv2dFamily::wide);
+    if (halo_route(*a32, 32, true, false, r)) return is(Conv2dFamily::halo);
+    r.k32 = false;
+  }
+  // the 16-K packing's LDS-tiled kernels (thin 3x3 layers, 16-channel slices), the bf16 wide kernel
+  if (lds3_route(a, f32)) return is(Conv2dFamily::lds3);
+  if (lds_s2_route(a)) return is(Conv2dFamily::lds_s2);
+  if (halo_route(a, KC, false, !f32, r)) return is(Conv2dFamily::halo);
+  if (!f32 && wide_route(a, false, r)) return is(Conv2dFamily::wide);
+  // the gather kernel, fp32 on the 32-K packing where the layer has one. Widest cout tile (each loaded input fragment
+  // feeds MT MFMAs) that still puts about one wave on every SIMD: the low-resolution GeoFeatureFusion layers have few
+  // pixels and many channels.
+  r.k32 = a32 && gather32_ok(*a32);
+  r.mt = gather_mt(a, !f32);
+  return is(r.k32 ? Conv2dFamily::gather32 : Conv2dFamily::gather);
+}
+
+template <typename T>
+hipError_t launch_route(hipStream_t s, const Conv2dRoute& r, const Conv2dArgs& a) {  // a: on the packing r names
+  switch (r.family) {
+    case Conv2dFamily::planes: return launch_conv2d_planes(s, sizeof(T) == 2 ? ST_BF16 : ST_F32, a);
+    case Conv2dFamily::xpair_lds: {
       const int tx = (a.Wq + L2W - 1) / L2W, ty = (a.Hq + L2H - 1) / L2H;
       const long long nt = (long long)tx * ty * a.B;
       hipLaunchKernelGGL(conv2d_xpair_lds_kernel<T>, dim3((unsigned)nt), dim3(256), 0, s, a, tx, ty, (int)nt);
       return hipGetLastError();
     }
-    const long long Qtot = (long long)a.B * a.Hq * a.Wq;
-    const int nq = (int)((Qtot + 4LL * kG2 * 16 - 1) / (4LL * kG2 * 16));
-    const dim3 grid((unsigned)(nq * a.nphase), 1);
-    if (a.c1 > 0)
-      hipLaunchKernelGGL((conv2d_mfma_kernel<T, 1, true, true>), grid, dim3(256), 0, s, a, nq);
-    else
-      hipLaunchKernelGGL((conv2d_mfma_kernel<T, 1, false, true>), grid, dim3(256), 0, s, a, nq);
-    return hipGetLastError();
-  }
-  {
-    hipError_t e = launch_lds2<T>(s, a);
-    if (e != hipErrorNotSupported) return e;
-    e = launch_lds_s2<T>(s, a);
-    if (e != hipErrorNotSupported) return e;
-    e = launch_halo<T>(s, a);
-    if (e != hipErrorNotSupported) return e;
-    if constexpr (T_is_bf16<T>::value) {
-      e = launch_wide<T>(s, a);
-      if (e != hipErrorNotSupported) return e;
+    case Conv2dFamily::xpair_gather: {
+      const long long Qtot = (long long)a.B * a.Hq * a.Wq;
+      const int nq = (int)((Qtot + 4LL * kG2 * 16 - 1) / (4LL * kG2 * 16));
+      const dim3 grid((unsigned)(nq * a.nphase), 1);
+      if (a.c1 > 0)
+        hipLaunchKernelGGL((conv2d_mfma_kernel<T, 1, true, true>), grid, dim3(256), 0, s, a, nq);
+      else
+        hipLaunchKernelGGL((conv2d_mfma_kernel<T, 1, false, true>), grid, dim3(256), 0, s, a, nq);
+      return hipGetLastError();
     }
+    case Conv2dFamily::lds3: return launch_lds3<T>(s, a);
+    case Conv2dFamily::lds_s2: return launch_lds_s2<T>(s, a);
+    case Conv2dFamily::halo: return launch_halo<T>(s, a, r);
+    case Conv2dFamily::wide: return launch_wide<T>(s, a, r);
+    case Conv2dFamily::gather32:
+      if constexpr (sizeof(T) == 4) {
+        if (r.mt == 4) return launch_mt<T, 4, true>(s, a);
+        return r.mt == 2 ? launch_mt<T, 2, true>(s, a) : launch_mt<T, 1, true>(s, a);
+      }
+      return hipErrorInvalidValue;
+    case Conv2dFamily::gather:
+      if (r.mt == 8) return launch_mt<T, 8>(s, a);
+      if (r.mt == 4) return launch_mt<T, 4>(s, a);
+      return r.mt == 2 ? launch_mt<T, 2>(s, a) : launch_mt<T, 1>(s, a);
+    case Conv2dFamily::invalid: break;
   }
-  // Widest cout tile (each loaded input fragment feeds MT MFMAs) that still puts about one wave on
-  // every SIMD: the low-resolution GeoFeatureFusion layers have few pixels and many channels.
-  const int gmt = gather_mt(a, T_is_bf16<T>::value);
-  if (gmt == 8) return launch_mt<T, 8>(s, a);
-  if (gmt == 4) return launch_mt<T, 4>(s, a);
-  if (gmt == 2) return launch_mt<T, 2>(s, a);
-  return launch_mt<T, 1>(s, a);
+  return hipErrorInvalidValue;
 }
 
 // Border correction of a 3x3 padding-1 conv whose bias was the full 9-tap sum: at each border pixel
@@ -2303,13 +2312,10 @@ hipError_t launch_border_bias(hipStream_t s, int store, const BorderArgs& a, int
   return hipGetLastError();
 }
 
-bool conv2d_wide_shape_ok(const Conv2dArgs& a) {
-  int dmin = 0, span = 0;
-  return wide_shape_ok(a, dmin, span);
-}
-
-hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a) {
-  return store == ST_BF16 ? launch_t<bf16_t>(s, a) : launch_t<float>(s, a);
+hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a, const Conv2dArgs* a32) {
+  const Conv2dRoute r = conv2d_route(a, a32, store);
+  const Conv2dArgs& p = r.k32 ? *a32 : a;
+  return store == ST_BF16 ? launch_route<bf16_t>(s, r, p) : launch_route<float>(s, r, p);
 }
 
 }  // namespace damvs

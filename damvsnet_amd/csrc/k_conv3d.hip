@@ -1188,14 +1188,8 @@ hipError_t launch_dz_t(hipStream_t s, const ConvArgs& a) {
   constexpr int zc = 16;
   const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + 2 * RP - 1) / (2 * RP), nzc = (a.Do + zc - 1) / zc;
   const long long nt = (long long)tx * ty * nzc * a.B;
-  auto k = conv0_dz_kernel<CIN, RP, TXG>;
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(192 * RP), smem, s, a, tx, ty, nzc, zc, (int)nt);
-  return hipGetLastError();
+  return launch_big_lds(conv0_dz_kernel<CIN, RP, TXG>, dim3((unsigned)nt), dim3(192 * RP), smem, s, a, tx, ty, nzc, zc,
+                        (int)nt);
 }
 
 // DAMVS_CONV0_DZ (read per call): "0" = off (the input-plane walk / output-plane walk as DAMVS_CONV0_REUSE says), "1"
@@ -1205,7 +1199,7 @@ hipError_t launch_dz_t(hipStream_t s, const ConvArgs& a) {
 // B fragment's three split MFMAs depend on each other, where the walk interleaves three depths' accumulators; at CIN 32
 // the three waves per SIMD (against one) cover that latency.
 bool conv0_dz_shape(int CIN, int& rp, int& txg) {
-  const char* v = getenv("DAMVS_CONV0_DZ");
+  const char* v = switch_value(SW_CONV0_DZ);
   rp = 4;
   txg = CIN == 8 ? 2 : 1;
   if (!v || !v[0]) return CIN == 32;  // unset or empty: the default
@@ -1231,11 +1225,6 @@ hipError_t launch_dz(hipStream_t s, const ConvArgs& a, int rp, int txg) {
   return hipErrorInvalidValue;
 }
 
-bool zslide_disabled() {  // read per call: tests flip it between launches
-  const char* v = getenv("DAMVS_CONV_NO_ZSLIDE");
-  return v && v[0] == '1';
-}
-
 template <typename T, int CIN, int TXG>
 hipError_t launch_zslide_pair_t(hipStream_t s, const ConvArgs& a) {
   constexpr int PLANE = (LTH + 2) * (16 * TXG + 2) * (CIN / 8) * ZForm<T>::PL;
@@ -1243,14 +1232,8 @@ hipError_t launch_zslide_pair_t(hipStream_t s, const ConvArgs& a) {
   constexpr int zc = 16;  // z-planes per block; measured: 16 beats 8 and 32 over stages 1-2 at B=4
   const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + LTH - 1) / LTH, nzc = (a.Do + zc - 1) / zc;
   const long long nt = (long long)tx * ty * nzc * a.B;
-  auto k = conv3d_zslide_pair_kernel<T, CIN, TXG>;
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)smem);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc, (int)nt);
-  return hipGetLastError();
+  return launch_big_lds(conv3d_zslide_pair_kernel<T, CIN, TXG>, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc,
+                        (int)nt);
 }
 
 // conv0 on the input-plane walk (conv3d_zreuse_pair_kernel, 2-slot ring)
@@ -1269,10 +1252,10 @@ hipError_t launch_zreuse_pair_t(hipStream_t s, const ConvArgs& a) {
 template <typename T, int CIN>
 hipError_t launch_lds_pair_t(hipStream_t s, const ConvArgs& a) {
   if constexpr (sizeof(T) == 2) {
-    if (!a.resid && !zslide_disabled()) {
+    if (!a.resid && !switch_on(SW_CONV_NO_ZSLIDE)) {
       // DAMVS_CONV0_REUSE (read per call): 1 = the input-plane walk at every CIN, 0 = never; default: CIN 32 only
       // (at CIN 8 / 16 its registers cost a wave per SIMD: stage 2 / 3 U-Net 2.09 / 1.89 -> 2.22 / 2.01 ms)
-      const char* rv = getenv("DAMVS_CONV0_REUSE");
+      const char* rv = switch_value(SW_CONV0_REUSE);
       const bool reuse = rv ? rv[0] == '1' : CIN == 32;
       if (reuse) return launch_zreuse_pair_t<T, CIN, 2>(s, a);
       if constexpr (CIN == 32) return launch_zslide_pair_t<T, CIN, 1>(s, a);
@@ -1281,44 +1264,30 @@ hipError_t launch_lds_pair_t(hipStream_t s, const ConvArgs& a) {
   } else {
     // fp32: the split-f16 z-streamed kernel on the 32-K row-pair packing, A fragments in registers (CIN 32: 36 pairs,
     // 288 VGPRs, with the 92 KB ring one block and one wave per SIMD)
-    if (!a.resid && a.wpack32 && !zslide_disabled()) {
+    if (!a.resid && a.wpack32 && !switch_on(SW_CONV_NO_ZSLIDE)) {
       int rp, txg;
       if (conv0_dz_shape(CIN, rp, txg)) return launch_dz<CIN>(s, a, rp, txg);
       // DAMVS_CONV0_REUSE (read per call): 1 = the input-plane walk, 0 = the output-plane walk; default: the walk at CIN
       // 16 / 32 (bitwise equal, test_conv0_reuse_fp32_bitwise)
-      const char* rv = getenv("DAMVS_CONV0_REUSE");
+      const char* rv = switch_value(SW_CONV0_REUSE);
       const bool reuse = rv ? rv[0] == '1' : CIN >= 16;
       if (reuse) return launch_zreuse_pair_t<T, CIN, CIN >= 16 ? 1 : 2>(s, a);
       if constexpr (CIN >= 16) return launch_zslide_pair_t<T, CIN, 1>(s, a);  // 8 x 16 windows, no spill
       else return launch_zslide_pair_t<T, CIN, 2>(s, a);
     }
   }
-  const size_t smem = lds_tile_bytes<T, CIN>();
-  auto k = conv3d_lds_pair_kernel<T, CIN>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)smem);
-    if (e != hipSuccess) return e;
-  }
   const int tx = (a.Wo + LTW - 1) / LTW, ty = (a.Ho + LTH - 1) / LTH, tz = (a.Do + LTD - 1) / LTD;
   const long long nt = (long long)tx * ty * tz * a.B;
-  hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, tz, (int)nt);
-  return hipGetLastError();
+  return launch_big_lds(conv3d_lds_pair_kernel<T, CIN>, dim3((unsigned)nt), dim3(256), lds_tile_bytes<T, CIN>(), s, a, tx,
+                        ty, tz, (int)nt);
 }
 
 template <typename T, int CIN, int MT>
 hipError_t launch_lds_t(hipStream_t s, const ConvArgs& a) {
-  const size_t smem = lds_tile_bytes<T, CIN>();
-  auto k = conv3d_lds_kernel<T, CIN, MT>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)smem);
-    if (e != hipSuccess) return e;
-  }
   const int tx = (a.Wo + LTW - 1) / LTW, ty = (a.Ho + LTH - 1) / LTH, tz = (a.Do + LTD - 1) / LTD;
   const long long nt = (long long)tx * ty * tz * a.B;
-  hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, tz, (int)nt);
-  return hipGetLastError();
+  return launch_big_lds(conv3d_lds_kernel<T, CIN, MT>, dim3((unsigned)nt), dim3(256), lds_tile_bytes<T, CIN>(), s, a, tx,
+                        ty, tz, (int)nt);
 }
 
 // conv2 (Conv3d k3 s1 p1, 16 -> 16 channels) streamed along z on conv0's plan (4-slot ring of
@@ -1472,7 +1441,7 @@ hipError_t launch_lds(hipStream_t s, const ConvArgs& a) {
     if (a.Cin == 16) return launch_lds_pair_t<T, 16>(s, a);
     if (a.Cin == 32) return launch_lds_pair_t<T, 32>(s, a);  // fp32: the 138 KB tile (one block per CU)
   }
-  if ((sizeof(T) == 2 || a.wpack32) && a.Cin == 16 && a.Cout == 16 && MT == 1 && !a.resid && !zslide_disabled()) {
+  if ((sizeof(T) == 2 || a.wpack32) && a.Cin == 16 && a.Cout == 16 && MT == 1 && !a.resid && !switch_on(SW_CONV_NO_ZSLIDE)) {
     constexpr int zc = 16, TXG = sizeof(T) == 2 ? 2 : 1;
     const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + LTH - 1) / LTH, nzc = (a.Do + zc - 1) / zc;
     const long long nt = (long long)tx * ty * nzc * a.B;
@@ -2029,19 +1998,14 @@ __global__ __launch_bounds__(256) void conv_s2_c8_zslide_kernel(const ConvArgs a
   am_flush<T>(a, am, b, blockIdx.x * 4 + wave);
 }
 
-bool deconv_zslide_disabled() {  // read per call: tests flip it between launches
-  const char* v = getenv("DAMVS_DECONV_NO_ZSLIDE");
-  return v && v[0] == '1';
-}
-
 template <typename T>
 hipError_t launch_t(hipStream_t s, const ConvArgs& a) {
   long long Qtot = (long long)a.B * a.Dq * a.Hq * a.Wq;
   long long per_block = 4LL * kGroups * 16;
   const int nq = (int)((Qtot + per_block - 1) / per_block);
   dim3 grid((unsigned)(nq * a.nphase));
-  if ((sizeof(T) == 2 || a.wpack32) && a.xpair && a.Cin == 16 && a.Cout == 8 && a.nphase == 4 &&
-      !deconv_zslide_disabled()) {
+  const bool zslide = !switch_on(SW_DECONV_NO_ZSLIDE);  // read per call: tests flip it between launches
+  if ((sizeof(T) == 2 || a.wpack32) && a.xpair && a.Cin == 16 && a.Cout == 8 && a.nphase == 4 && zslide) {
     constexpr int zc = 8;
     const int tx = (a.Wi + 15) / 16, ty = (a.Hi + 7) / 8, nzc = (a.Di + zc - 1) / zc;
     const long long nt = (long long)tx * ty * nzc * a.B;
@@ -2052,22 +2016,14 @@ hipError_t launch_t(hipStream_t s, const ConvArgs& a) {
     return hipGetLastError();
   }
   if ((sizeof(T) == 2 || a.wpack32) && a.nphase == 1 && a.in_stride == 2 && a.Cin == 8 && a.Cout == 16 && a.MT == 1 &&
-      !a.resid && a.ph[0].ntaps == 27 && !deconv_zslide_disabled()) {
+      !a.resid && a.ph[0].ntaps == 27 && zslide) {
     constexpr int zc = 8;
     const int tx = (a.Wo + 15) / 16, ty = (a.Ho + 7) / 8, nzc = (a.Do + zc - 1) / zc;
     const long long nt = (long long)tx * ty * nzc * a.B;
     const size_t smem = sizeof(T) == 2 ? 5 * 17 * 33 * 16 : 4 * 17 * 34 * 32;  // ring slots (NS) x plane
-    auto k = conv_s2_c8_zslide_kernel<T>;
-    if (smem > 64 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc, (int)nt);
-    return hipGetLastError();
+    return launch_big_lds(conv_s2_c8_zslide_kernel<T>, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc, (int)nt);
   }
-  if ((sizeof(T) == 2 || a.wpack32) && !a.xpair && a.nphase == 8 && a.Cin == 32 && a.Cout == 16 && a.MT == 1 &&
-      !deconv_zslide_disabled()) {
+  if ((sizeof(T) == 2 || a.wpack32) && !a.xpair && a.nphase == 8 && a.Cin == 32 && a.Cout == 16 && a.MT == 1 && zslide) {
     constexpr int zc = 8;
     const int tx = (a.Wi + 15) / 16, ty = (a.Hi + 7) / 8, nzc = (a.Di + zc - 1) / zc;
     const long long nt = (long long)tx * ty * nzc * a.B;
@@ -2077,14 +2033,11 @@ hipError_t launch_t(hipStream_t s, const ConvArgs& a) {
       // 2.071-2.102 / 1.879-1.884 -> 1.128-1.129 / 2.020-2.024 / 1.826-1.837 ms (profiles/r03/ab_conv9.jsonl)
       hipLaunchKernelGGL((deconv_c16_zslide_kernel<T, true>), dim3((unsigned)nt), dim3(256), ring + 27 * 64 * 16, s, a,
                          tx, ty, nzc, zc, (int)nt);
-    } else {
-      auto k = deconv_c16_zslide_kernel<T, false>;
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k, dim3((unsigned)nt), dim3(256), ring, s, a, tx, ty, nzc, zc, (int)nt);
+      return hipGetLastError();
+    } else {  // the fp32 ring is 78,336 bytes
+      return launch_big_lds(deconv_c16_zslide_kernel<T, false>, dim3((unsigned)nt), dim3(256), ring, s, a, tx, ty, nzc, zc,
+                            (int)nt);
     }
-    return hipGetLastError();
   }
   if (sizeof(T) == 4 && a.B > 1 && (a.in_amax || a.out_amax) && a.Dq * a.Hq * a.Wq < kGroups * 16) {
     // the gather kernel's waves straddle at most two batch elements (per-voxel prescales); a q-grid of fewer voxels
@@ -2110,8 +2063,7 @@ hipError_t launch_t(hipStream_t s, const ConvArgs& a) {
   }
   if constexpr (sizeof(T) == 4) {
     // fp32: the 32-K split form where the layer has its packing (DAMVS_CONV3D_K16=1, read per call: the 16-K form)
-    const char* kv = getenv("DAMVS_CONV3D_K16");
-    if (a.wgat32 && !(kv && kv[0] == '1')) {
+    if (a.wgat32 && !switch_on(SW_CONV3D_K16)) {
       ConvArgs a2 = a;
       for (int p = 0; p < a.nphase; ++p) {  // the phases of the 32-K packing (LayerPlan, build_phases(., 32))
         a2.ph[p].kchunks = a.k32_chunks[p];
@@ -2160,28 +2112,9 @@ hipError_t launch_conv3d(hipStream_t s, int store, const ConvArgs& a0) {
     return hipSuccess;
   }
   if (in_b >= (1LL << 31) || out_b >= (1LL << 31)) return hipErrorInvalidValue;
-  if (!conv_lds_disabled()) {
-    hipError_t e = store == ST_BF16 ? launch_lds<bf16_t>(s, a) : launch_lds<float>(s, a);
-    if (e != hipErrorNotSupported) return e;
-  }
+  const hipError_t e = store == ST_BF16 ? launch_lds<bf16_t>(s, a) : launch_lds<float>(s, a);
+  if (e != hipErrorNotSupported) return e;
   return store == ST_BF16 ? launch_t<bf16_t>(s, a) : launch_t<float>(s, a);
-}
-
-// The x-pair conv11 runs by default; DAMVS_CONV_XPAIR=0 selects the 8-phase form (A/B and diagnosis).
-bool conv_xpair_disabled() {
-  static const bool off = [] {
-    const char* v = getenv("DAMVS_CONV_XPAIR");
-    return v && v[0] == '0';
-  }();
-  return off;
-}
-
-bool conv_lds_disabled() {
-  static const bool off = [] {
-    const char* v = getenv("DAMVS_CONV_NO_LDS");
-    return v && v[0] == '1';
-  }();
-  return off;
 }
 
 }  // namespace damvs

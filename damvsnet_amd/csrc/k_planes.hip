@@ -379,8 +379,7 @@ hipError_t launch_planes4_k(hipStream_t st, const Conv2dArgs& a) {
 // conv2d_planes4_kernel's conditions: 4-column groups of whole 16-byte plane pieces (DAMVS_PLANES4=0, read per call:
 // the one-column kernel)
 bool planes4_ok(const Conv2dArgs& a) {
-  const char* v = getenv("DAMVS_PLANES4");
-  if ((v && v[0] == '0') || a.cout > 8 || a.Wi % 4 || a.Wo != a.Wi) return false;
+  if (!switch_on(SW_PLANES4) || a.cout > 8 || a.Wi % 4 || a.Wo != a.Wi) return false;
   for (int g = 0; g < a.ngeo; ++g)
     if (reinterpret_cast<uintptr_t>(a.geo[g]) % 16 || a.geo_bstride[g] % 4) return false;
   return true;
@@ -402,8 +401,7 @@ hipError_t launch_planes_k(hipStream_t st, const Conv2dArgs& a) {
 // conv2d_planes_mfma_kernel's conditions (on top of planes_fast_ok): cout 4 or 8, whole 16-byte plane pieces, 32-bit
 // byte offsets
 bool planes_mfma_ok(const Conv2dArgs& a) {
-  const char* v = getenv("DAMVS_PLANES_MFMA");
-  if ((v && v[0] == '0') || (a.cout != 4 && a.cout != 8) || a.Wi % 4 || a.Wo != a.Wi || a.Ho != a.Hi) return false;
+  if (!switch_on(SW_PLANES_MFMA) || (a.cout != 4 && a.cout != 8) || a.Wi % 4 || a.Wo != a.Wi || a.Ho != a.Hi) return false;
   for (int g = 0; g < a.ngeo; ++g)
     if (reinterpret_cast<uintptr_t>(a.geo[g]) % 16 || a.geo_bstride[g] % 4 ||
         ((long long)(a.B - 1) * a.geo_bstride[g] + (long long)a.Hi * a.Wi) * 4 >= (1LL << 31))
@@ -414,12 +412,9 @@ bool planes_mfma_ok(const Conv2dArgs& a) {
 template <typename T, int K>
 hipError_t launch_planes_mfma_k(hipStream_t st, const Conv2dArgs& a) {
   const int tx = (a.Wo + 63) / 64, ty = (a.Ho + 15) / 16;
-  // tiles per block (DAMVS_PLANES_NT, read per call, 1-16; default 4: FeatureNet's RGB conv x20 / GeoFF RGB+depth /
-  // depth init at B=4, bf16, 405 / 117 / 73 us at 1 tile, 354 / 99 / 62 at 2, 326 / 93 / 59 at 4, 324 / 92 / 59 at 8,
-  // profiles/r06/ab_planes_mfma)
-  const char* v = getenv("DAMVS_PLANES_NT");
-  int nt = v && v[0] ? atoi(v) : 4;
-  nt = nt < 1 ? 1 : nt > 16 ? 16 : nt;
+  // tiles per block: FeatureNet's RGB conv x20 / GeoFF RGB+depth / depth init at B=4, bf16, 405 / 117 / 73 us at 1
+  // tile, 354 / 99 / 62 at 2, 326 / 93 / 59 at 4, 324 / 92 / 59 at 8 (profiles/r06/ab_planes_mfma)
+  constexpr int nt = 4;
   const dim3 grid((unsigned)(tx * ((ty + nt - 1) / nt) * a.B));
   switch (a.ngeo) {
     case 1: hipLaunchKernelGGL((conv2d_planes_mfma_kernel<T, K, 1>), grid, dim3(256), 0, st, a, tx, ty, nt); break;

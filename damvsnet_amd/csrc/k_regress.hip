@@ -527,16 +527,9 @@ hipError_t launch_pr_t(hipStream_t s, int B, int D, int h, int w, const void* fe
   const size_t smem = prob_regress_smem<T, CB>(D);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
   if ((long long)D * h * w * CB * (long long)sizeof(T) >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit offsets
-  auto k = prob_regress_kernel<T, CB, false>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)smem);
-    if (e != hipSuccess) return e;
-  }
   dim3 grid((w + kTX - 1) / kTX, (h + kTY - 1) / kTY, B);
-  hipLaunchKernelGGL(k, grid, dim3(256), smem, s, B, D, h, w, reinterpret_cast<const T*>(feat), wprob, prob_init, hyps,
-                     depth, conf, var, prob);
-  return hipGetLastError();
+  return launch_big_lds(prob_regress_kernel<T, CB, false>, grid, dim3(256), smem, s, B, D, h, w,
+                        reinterpret_cast<const T*>(feat), wprob, prob_init, hyps, depth, conf, var, prob);
 }
 
 template <typename T, int CB>
@@ -647,38 +640,24 @@ hipError_t launch_prob_mfma(hipStream_t s, int store, int B, int D, int h, int w
   const int PL = store == ST_BF16 ? 1 : 2;
   if (D < 1 || smem > 160 * 1024) return hipErrorInvalidValue;
   if ((long long)B * D * h * w * 16 * PL >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit buffer offsets
-  const void* k = store == ST_BF16 ? reinterpret_cast<const void*>(prob_mfma_kernel<bf16_t>)
-                                   : reinterpret_cast<const void*>(prob_mfma_kernel<float>);
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return e;
-  }
   const dim3 grid((w + kTX - 1) / kTX, (h + kTY - 1) / kTY, B);
   // 16-byte probability stores need w % 4 == 0 (DAMVS_PROB_VEC=0, read per call: one 4-byte store per pixel and plane)
-  const char* pv = getenv("DAMVS_PROB_VEC");
-  const int vec_ok = (w & 3) == 0 && !(pv && pv[0] == '0');
+  const int vec_ok = (w & 3) == 0 && switch_on(SW_PROB_VEC);
   if (store == ST_BF16)
-    hipLaunchKernelGGL(prob_mfma_kernel<bf16_t>, grid, dim3(256), smem, s, B, D, h, w,
-                       reinterpret_cast<const bf16_t*>(feat), reinterpret_cast<const uint4*>(apack), 1.f, prob_init,
-                       hyps, depth, conf, var, prob, vec_ok);
-  else
-    hipLaunchKernelGGL(prob_mfma_kernel<float>, grid, dim3(256), smem, s, B, D, h, w,
-                       reinterpret_cast<const float*>(feat), reinterpret_cast<const uint4*>(apack), pscale, prob_init,
-                       hyps, depth, conf, var, prob, vec_ok);
-  return hipGetLastError();
+    return launch_big_lds(prob_mfma_kernel<bf16_t>, grid, dim3(256), smem, s, B, D, h, w,
+                          reinterpret_cast<const bf16_t*>(feat), reinterpret_cast<const uint4*>(apack), 1.f, prob_init,
+                          hyps, depth, conf, var, prob, vec_ok);
+  return launch_big_lds(prob_mfma_kernel<float>, grid, dim3(256), smem, s, B, D, h, w,
+                        reinterpret_cast<const float*>(feat), reinterpret_cast<const uint4*>(apack), pscale, prob_init,
+                        hyps, depth, conf, var, prob, vec_ok);
 }
 
-// DAMVS_PROB_MFMA=0 (read per call: tests flip it) sends bf16 stages to the VALU prob_regress_kernel.
-bool prob_mfma_disabled() {
-  const char* v = getenv("DAMVS_PROB_MFMA");
-  return v && v[0] == '0';
-}
-
-// The stage regression's prob conv on MFMA for this storage type: bf16 by default; fp32 (the split-f16 form) only
+// The stage regression's prob conv on MFMA for this storage type: bf16 by default (DAMVS_PROB_MFMA=0, read per call:
+// the VALU prob_regress_kernel); fp32 (the split-f16 form) only
 // with DAMVS_PROB_MFMA=1 -- three MFMAs per product measured slower than the VALU kernel (cfgC B=4 fp32: 1.66
 // against 1.56 ms per step, profiles/r04/prof_steps_f32_r04j.txt).
 bool prob_mfma_enabled(int store) {
-  const char* v = getenv("DAMVS_PROB_MFMA");
+  const char* v = switch_value(SW_PROB_MFMA);
   if (v && v[0] == '0') return false;
   return store == ST_BF16 || (v && v[0] == '1');
 }

@@ -545,23 +545,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, kWarpBlock))) void warp
 
 // Lanes per voxel the launcher uses for C-channel maps: the channel-split kernel for NHWC maps of 2, 4 or 8 16-byte
 // chunks per pixel when the view pipeline takes the view count (odd N >= 3), else 1 (the one-lane kernel).
-// DAMVS_WARP_SPLIT=0 (one lane per voxel everywhere) and DAMVS_WARP_NO_PIPE=1 (no view pipeline) both give 1, so the
-// launcher's block geometry and launch_k's kernel choice follow one predicate.
-bool warp_no_pipe() {
-  static const bool v = [] {
-    const char* e = getenv("DAMVS_WARP_NO_PIPE");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-bool warp_split_enabled() {
-  static const bool off = [] {
-    const char* v = getenv("DAMVS_WARP_SPLIT");
-    return v && v[0] == '0';
-  }();
-  return !off && !warp_no_pipe();
-}
-
+// DAMVS_WARP_SPLIT=0 (one lane per voxel everywhere) gives 1 too; the launcher's block geometry and launch_k's kernel
+// choice follow this one predicate.
 template <typename T, int C, bool BLK>
 int split_lanes(const WarpArgs& a) {
   constexpr int S = C * (int)sizeof(T) / 16;
@@ -570,11 +555,7 @@ int split_lanes(const WarpArgs& a) {
 
 template <typename T, int C, int MODE, bool BLK>
 void launch_k(hipStream_t s, const WarpArgs& a, dim3 grid, int npb, int dchunk, int ndc) {
-  const bool no_pipe = warp_no_pipe();
-  static const bool runtime_views = [] {  // DAMVS_WARP_RUNTIME_VIEWS=1: the runtime view loop for N = 5 too
-    const char* v = getenv("DAMVS_WARP_RUNTIME_VIEWS");
-    return v && v[0] == '1';
-  }();
+  const bool runtime_views = switch_on(SW_WARP_RUNTIME_VIEWS);  // 1: the runtime view loop for N = 5 / 7 too
   if constexpr (!BLK && (C * sizeof(T) == 32 || C * sizeof(T) == 64 || C * sizeof(T) == 128)) {
     if (split_lanes<T, C, BLK>(a) > 1) {
       // N = 5: the unrolled view loop at both storage types. Its fp32 form computed wrong voxels in lanes 48-63 beside
@@ -597,7 +578,7 @@ void launch_k(hipStream_t s, const WarpArgs& a, dim3 grid, int npb, int dchunk, 
   // view pipeline: unrolled for N = 5 (the DTU default) at 16 channels (stage 2; A/B: 2.29 against 2.37 ms, while
   // stage 3 runs 1.47 against 1.50 ms on the runtime loop), a runtime view loop for any other odd
   // N (7, 11: the cfgD / cfgE benchmark configs; 3) and for 32 channels (the unrolled form needs 360 registers)
-  const bool pipe = !no_pipe && a.N >= 3 && (a.N - 1) % 2 == 0;
+  const bool pipe = a.N >= 3 && (a.N - 1) % 2 == 0;
   if constexpr (C == 16) {
     if (pipe && a.N == 5 && !runtime_views) {
       hipLaunchKernelGGL((warp_aggregate_kernel<T, C, MODE, BLK, 4>), grid, dim3(kWarpBlock), 0, s, a, a.rt, npb, dchunk, ndc);
@@ -628,30 +609,18 @@ hipError_t launch_c(hipStream_t s, const WarpArgs& a0) {
     case 32: pick(IntC<32>()); break;
   }
   const int ppb = block / lanes;
-  // Pixel blocks as R-row tiles (R divides ppb) dealt across the full width, or in strips SW pixels wide:
-  // DAMVS_WARP_TILE="R,SW", default R = 8; "0": ppb consecutive pixels of the row-major computed rows. The
+  // Pixel blocks as R-row tiles (R = 8 divides ppb) dealt across the full width, top to bottom. The
   // 8-row tiles keep vertically adjacent pixels, whose bilinear footprints share source rows, on one CU: stage-2
   // L1 -> L2 requests -19 % and L2 hit 0.62 -> 0.71 already at 4 rows (profiles/r03/pmc_l2_tile.json); in the
   // pipeline (B=4) stage 3 1.48 -> 1.24 ms, stage 2 2.00 -> 1.82 ms, stage 1 1.40 -> 1.31 ms; 16 / 32 / 64 rows
   // slower again (profiles/r03/ab_warp_tile.jsonl).
-  static const int tile_env[2] = {[] {
-                                    const char* e = getenv("DAMVS_WARP_TILE");
-                                    return e ? atoi(e) : 8;
-                                  }(),
-                                  [] {
-                                    const char* e = getenv("DAMVS_WARP_TILE");
-                                    const char* c = e ? strchr(e, ',') : nullptr;
-                                    return c ? atoi(c + 1) : 0;
-                                  }()};
-  a.tile_r = 0;
-  int npb = (a.rows * a.w + ppb - 1) / ppb;
-  if (tile_env[0] > 0 && ppb % tile_env[0] == 0) {
-    const int tc = ppb / tile_env[0];
-    a.tile_r = tile_env[0];
-    a.tiles_x = (a.w + tc - 1) / tc;
-    a.tile_sw = tile_env[1] >= tc ? std::min(a.tiles_x, tile_env[1] / tc) : a.tiles_x;
-    npb = a.tiles_x * ((a.rows + a.tile_r - 1) / a.tile_r);
-  }
+  constexpr int R = 8;
+  static_assert(kWarpBlock / 8 % R == 0, "every lane count (1, 2, 4, 8) leaves whole R-row tiles");
+  const int tc = ppb / R;
+  a.tile_r = R;
+  a.tiles_x = (a.w + tc - 1) / tc;
+  a.tile_sw = a.tiles_x;
+  const int npb = a.tiles_x * ((a.rows + a.tile_r - 1) / a.tile_r);
   // depth chunk: as long as possible (locality) while keeping >= ~4 blocks per CU in flight
   int dchunk = a.D;
   // (in 256-thread blocks: 512 - 32768 measured flat within 3 %, 16384+ slower in the pipeline)
@@ -715,7 +684,7 @@ __global__ __launch_bounds__(256) void block_channels_kernel(const FeatPtrs src,
 // Whether launch_warp_aggregate runs the channel-split kernel for NHWC maps of `bytes`-byte pixels at N views (the
 // predicate split_lanes applies per launch; capi's feature-layout choice asks it before the maps are laid out).
 bool warp_split_for(int bytes, int N) {
-  return warp_split_enabled() && (bytes == 32 || bytes == 64 || bytes == 128) && N >= 3 && (N - 1) % 2 == 0;
+  return switch_on(SW_WARP_SPLIT) && (bytes == 32 || bytes == 64 || bytes == 128) && N >= 3 && (N - 1) % 2 == 0;
 }
 
 hipError_t launch_warp_aggregate(hipStream_t s, int store, int mode, const WarpArgs& a, bool blocked) {

@@ -1,8 +1,9 @@
-"""Diagnose run-to-run differences of the bf16 U-Net (x-pair conv11 on/off via DAMVS_CONV_XPAIR set by
-the caller): runs costreg_logits repeatedly on one volume and reports, per run, which regions of
-the workspace (the U-Net's level buffers) and the logits differ from run 0.
+"""Diagnose run-to-run differences of the bf16 U-Net (conv11 on its x-pair kernels; the switch that selected its
+8-phase form was removed, so that form needs a source edit and a DAMVS_LIB build): runs costreg_logits repeatedly on
+one volume and reports, per run, which regions of the workspace (the U-Net's level buffers) and the logits differ from
+run 0.
 
-  DAMVS_CONV_XPAIR=1 python tools/diag_unet_repro.py [--D 64 --stage 0 --runs 6]
+  python tools/diag_unet_repro.py [--D 64 --stage 0 --runs 6]
 """
 import argparse
 import os
@@ -41,7 +42,7 @@ def main():
     nhwc = [f.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).to(dev) for f in feats]
     vol = eng.warp_aggregate(nhwc, P.to(dev), hyps.to(dev))
     B, D, h, w, _ = vol.shape
-    print("XPAIR env=%s  vol %s" % (os.environ.get("DAMVS_CONV_XPAIR"), tuple(vol.shape)), flush=True)
+    print("library %s  vol %s" % (os.environ.get("DAMVS_LIB", "in-tree"), tuple(vol.shape)), flush=True)
     snaps = []
     for r in range(args.runs):
         lg = eng.costreg_logits(vol)

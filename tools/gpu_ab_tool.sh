@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of one per-layer tool across environments / library builds in one GPU call: each argument is
-# "label|ENV=V ENV2=V2|tool args" (e.g. "s2 off|DAMVS_CONV2D_LDS_S2=0|tools/kbench2d.py --dtype f32 --only FA,FB";
+# "label|ENV=V ENV2=V2|tool args" (e.g. "g32 off|DAMVS_CONV2D_G32=0|tools/kbench2d.py --dtype f32 --only FA,FB";
 # "head|DAMVS_LIB=damvsnet_amd/ab/libdamvs_base.so|tools/unet_layers.py --dtype f32 --only conv11"). Each variant runs
 # as its own process under its own time limit; its output goes to gpurun_out/${TAG}_<n>.txt and its table lines to
 # stdout. Stops at the first failure. (Round 6's one-off A/B scripts, tools/gpu_r06*.sh up to commit 0fa9d58, were all of
