@@ -249,9 +249,6 @@ __device__ __forceinline__ float relu(float x) { return x < 0.f ? 0.f : x; }
 template <bool B> struct BoolC {
   static constexpr bool value = B;
 };
-template <int I> struct IntC {
-  static constexpr int value = I;
-};
 
 typedef unsigned int v4u32_t __attribute__((ext_vector_type(4)));
 typedef unsigned int v2u32_t __attribute__((ext_vector_type(2)));

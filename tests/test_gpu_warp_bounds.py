@@ -1,5 +1,6 @@
-"""Per-voxel bounded tests for the fused homography warp + cost aggregation (csrc/k_warp.hip: warp_aggregate_kernel,
-warp_split_kernel and the rows launch_k / launch_c pick among them) and for damvs_proj_prepare.
+"""Per-voxel bounded tests for the fused homography warp + cost aggregation (csrc/k_warp.hip: warp_aggregate_kernel and
+warp_split_kernel, which are one body, csrc/k_warp_body.h, at 1 and at 2 / 4 / 8 lanes per voxel, and the rows launch_k
+picks among them) and for damvs_proj_prepare.
 
 Every compared voxel must satisfy |got - ref| <= bound, where ref is a float64 numpy evaluation of the operation on
 the float32 operands the kernel receives (rt itself, the hypotheses, the features after their storage rounding, the
@@ -28,7 +29,7 @@ CPU part (not marked gpu): the liveness conditions of every case, a float32 rest
 staying inside the bound on every element (the gate is not too tight), four simulated defects each putting >= 25 % of
 the voxels outside it (the gate is not too loose), and the launcher's depth-chunk rule restated for the large cases.
 
-Depth chunks (launch_c: dchunk = D, halved (rounding up) while dchunk > 2 and pixel blocks x B x chunks < 2048 blocks
+Depth chunks (launch_k: dchunk = D, halved (rounding up) while dchunk > 2 and pixel blocks x B x chunks < 2048 blocks
 of 256 threads). The small shape B = 3, D = 5, h = 20, w = 42 gives chunks of 2, 2, 1 planes at every lane count; the
 large cases give
 
@@ -417,14 +418,14 @@ def restate_f32(fx, N, mode, net=None):
 # ---------------------------------------------------------------------------------------------- cases
 
 def lanes_per_voxel(C, bf16, N, blocked=False):
-    """k_warp.hip split_lanes: the channel-split kernel for NHWC maps of 2 / 4 / 8 16-byte chunks per pixel at odd
+    """k_warp.hip launch_k's lane count: the channel-split kernel for NHWC maps of 2 / 4 / 8 16-byte chunks per pixel at odd
     N >= 3, else one lane per voxel."""
     S = C * (2 if bf16 else 4) // 16
     return S if (not blocked and S in (2, 4, 8) and N >= 3 and N % 2 == 1) else 1
 
 
 def depth_chunks(B, D, h, w, lanes, rows=None):
-    """k_warp.hip launch_c restated: (dchunk, planes of the last chunk)."""
+    """k_warp.hip launch_k restated (tiles: warp_tiles.h): (dchunk, planes of the last chunk)."""
     rows = h if rows is None else rows
     tc = 256 // lanes // 8
     npb = -(-w // tc) * -(-rows // 8)

@@ -50,7 +50,7 @@ def main():
     es = feats[0].element_size()
     S = C * es // 16 if (C * es) in (32, 64, 128) else 1  # lanes per voxel of the split kernel (NHWC maps, odd N)
     ppb = 256 // S
-    tc = ppb // 8  # 8-row pixel tiles (warp_pixel; the launcher's R = 8)
+    tc = ppb // 8  # 8-row pixel tiles (warp_tiles.h: warp_pixel, kWarpTileRows)
 
     def waves(d):
         """Per wave instance (batch, tile, wave) whose voxels differ: planes hit, pixels per (wave, plane), lanes."""
