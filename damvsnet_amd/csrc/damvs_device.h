@@ -342,6 +342,69 @@ template <> struct Vox8<float> {
   }
 };
 
+// XCD-aware bijective block remap: blocks bid and bid + 8 run on one XCD, so each of the 8 XCDs gets a contiguous range
+// of the n logical blocks (neighbouring tiles' halos then hit that XCD's L2).
+__device__ __forceinline__ int xcd_block(int bid, int n) {
+  const int q8 = n / 8, r8 = n % 8, xcd = bid % 8;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+}
+// Block bid's tile of a (b, tz, ty, tx) grid, tx fastest, dealt by xcd_block.
+struct Tile4 { int tx, ty, tz, b; };
+__device__ __forceinline__ Tile4 tile4_of(int bid, int ntiles, int tiles_x, int tiles_y, int tiles_z) {
+  int tt = xcd_block(bid, ntiles);
+  Tile4 t;
+  t.tx = tt % tiles_x; tt /= tiles_x;
+  t.ty = tt % tiles_y; tt /= tiles_y;
+  t.tz = tt % tiles_z;
+  t.b = tt / tiles_z;
+  return t;
+}
+
+// Geometry of a z-streamed kernel's LDS ring, read by the kernel and by its launcher: a block of NT threads owns TX x TY
+// columns and streams (TY + HALO) x (TX + HALO) halo planes of CH 8-channel chunks per voxel through the ring's slots.
+template <typename T, int CH_, int TX_, int TY_, int HALO, int NT_ = 256>
+struct ZRing {
+  static constexpr int CH = CH_, TX = TX_, TY = TY_, NT = NT_;
+  static constexpr int S = CH * ZForm<T>::PL;               // 16-byte slots per voxel
+  static constexpr int PW = TX + HALO, PH = TY + HALO;      // voxels per plane row, rows per plane
+  static constexpr int PLANE = PH * PW * S;                 // 16-byte slots per plane
+  static constexpr int NLD = (PH * PW * CH + NT - 1) / NT;  // 8-channel chunks per thread per plane
+  static constexpr size_t bytes(int slots) { return (size_t)slots * PLANE * 16; }
+  // The plane stager. load: halo plane iz of batch element b, rows from iy0 and columns from ix0 (zero outside the
+  // volume), into this thread's registers. store: those registers into ring slot dst -- bf16 as loaded, fp32 times
+  // the prescale and split into the hi / lo slots at the column's swizzle (ZForm). Which slot is the kernel's policy.
+  static constexpr int PL = ZForm<T>::PL;
+  __device__ __forceinline__ static void load(__amdgpu_buffer_rsrc_t rin, const ConvArgs& a, int b, int iz, int iy0,
+                                              int ix0, uint4 (*v)[PL]) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int c = threadIdx.x + i * NT;
+      const int row = c / (PW * CH), col = c - row * (PW * CH);
+      const int iy = iy0 + row, ix = ix0 + col / CH;
+      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
+                      (unsigned)ix < (unsigned)a.Wi;
+      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + ix0) * CH + col) * (16u * PL);
+#pragma unroll
+      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
+    }
+  }
+  __device__ __forceinline__ static void store(uint4* dst, const uint4 (*v)[PL], float prescale) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int c = threadIdx.x + i * NT;
+      if (c >= PH * PW * CH) continue;
+      if constexpr (PL == 1) {
+        dst[c] = v[i][0];
+      } else {
+        const int vox = c / CH, q = c - vox * CH, sw = ZForm<T>::template zsw<S>(vox % PW);
+        const F16Pair p = split8s(v[i][0], v[i][1], prescale);
+        dst[vox * S + (q ^ sw)] = p.h;
+        dst[vox * S + ((CH + q) ^ sw)] = p.l;
+      }
+    }
+  }
+};
+
 // Stage N 16-byte chunks into LDS with a 256-thread block: chunk c = threadIdx.x + 256 i comes from
 // load(c). Loads are issued BATCH at a time before their ds_writes, so each lane keeps BATCH HBM
 // reads in flight (a plain strided `lds[c] = load(c)` loop waits for every load before its write:

@@ -52,8 +52,7 @@ __global__ __launch_bounds__(256) DAMVS_WAVES((sizeof(T) == 2 && MT == 4 && !TWO
   constexpr uint32_t ES = sizeof(T);
   // logical block = (q-block, phase), phase fastest, XCD-contiguous (see conv3d_mfma_kernel)
   const int nblk = nqblk * a.nphase;
-  const int bid = blockIdx.x, q8 = nblk / 8, r8 = nblk % 8, xcd = bid % 8;
-  const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  const int L = xcd_block(blockIdx.x, nblk);
   const int qblk = L / a.nphase;
   const Conv2dPhase& ph = a.ph[L - qblk * a.nphase];
   const int mt0 = blockIdx.y * MT;  // first 16-channel output tile of this block
@@ -348,8 +347,7 @@ __global__ __launch_bounds__(256) DAMVS_WAVES((sizeof(T) != 2 ? 1 : CIN == 32 ? 
   __shared__ float ptile[L2HH * L2HW];  // the plane's halo (a.ngeo == 1)
 
   // XCD-aware bijective remap (consecutive tiles along x share an XCD and its L2)
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  int tt = xcd_block(blockIdx.x, ntiles);
   const int tx = tt % tiles_x; tt /= tiles_x;
   const int ty = tt % tiles_y;
   const int b = tt / tiles_y;
@@ -508,8 +506,7 @@ __global__ __launch_bounds__(256) void conv2d_xpair_lds_kernel(const Conv2dArgs 
   __shared__ raw tile[TILE_CHUNKS];
   __shared__ int s_toff[2][16];  // per phase: tap t's halo offset in 16-byte chunks (-1: padding tap)
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  int tt = xcd_block(blockIdx.x, ntiles);
   const int tx = tt % tiles_x; tt /= tiles_x;
   const int ty = tt % tiles_y;
   const int b = tt / tiles_y;
@@ -638,8 +635,7 @@ __global__ __launch_bounds__(256) void conv2d_lds_s2_kernel(const Conv2dArgs a, 
   __shared__ raw tile[TILE_CHUNKS];
 
   // XCD-aware bijective remap (consecutive tiles along x share an XCD and its L2)
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  int tt = xcd_block(blockIdx.x, ntiles);
   const int tx = tt % tiles_x;
   tt /= tiles_x;
   const int ty = tt % tiles_y;
@@ -799,8 +795,7 @@ __global__ __launch_bounds__(256) void conv2d_halo_kernel(const Conv2dArgs a, in
   // logical block = (tile, phase), phase fastest, XCD-contiguous
   const int ntile = tiles_x * tiles_y * a.B;
   const int nblk = ntile * a.nphase;
-  const int bid = blockIdx.x, q8 = nblk / 8, r8 = nblk % 8, xcd = bid % 8;
-  const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  const int L = xcd_block(blockIdx.x, nblk);
   const int tl = L / a.nphase;
   const Conv2dPhase& ph = a.ph[L - tl * a.nphase];
   const int tx = tl % tiles_x, ty = (tl / tiles_x) % tiles_y, b = tl / (tiles_x * tiles_y);
@@ -1262,8 +1257,7 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? (IS == 1 || R1 ? 
   // logical block = (tile, phase), phase fastest, XCD-contiguous
   const int ntile = tiles_x * tiles_y * a.B;
   const int nblk = ntile * a.nphase;
-  const int bid = blockIdx.x, q8 = nblk / 8, r8 = nblk % 8, xcd = bid % 8;
-  const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  const int L = xcd_block(blockIdx.x, nblk);
   const int tl = L / a.nphase;
   const Conv2dPhase& ph = a.ph[L - tl * a.nphase];
   const int tx = tl % tiles_x, ty = (tl / tiles_x) % tiles_y, b = tl / (tiles_x * tiles_y);
@@ -2172,8 +2166,7 @@ __global__ __launch_bounds__(256) void fpn_top_kernel(const T* __restrict__ c0, 
   __shared__ uint4 sc0[C0_CHUNKS * PL];              // fp32: hi plane, then lo plane
   __shared__ uint4 sf[FR * FC * FS];
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  int tt = xcd_block(blockIdx.x, ntiles);
   const int tx = tt % tiles_x; tt /= tiles_x;
   const int ty = tt % tiles_y;
   const int b = tt / tiles_y;

@@ -19,6 +19,7 @@
 // zero-inserted transposed conv would carry.
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "damvs_device.h"
 
@@ -136,8 +137,7 @@ __global__ __launch_bounds__(256) DAMVS_WAVES((sizeof(T) == 2 && MT == 4 ? 3 : 1
   // parities of one deconv q-range run together on one XCD, so their interleaved half-line writes
   // (and the skip tensor's reads) merge in that L2.
   const int nblk = nqblk * a.nphase;
-  const int bid = blockIdx.x, q8 = nblk / 8, r8 = nblk % 8, xcd = bid % 8;
-  const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  const int L = xcd_block(blockIdx.x, nblk);
   const int qblk = L / a.nphase;
   const ConvPhase& ph = a.ph[L - qblk * a.nphase];
   __shared__ int s_tap[32];
@@ -397,13 +397,8 @@ __global__ __launch_bounds__(256) void conv3d_lds_kernel(const ConvArgs a, int t
   raw* tile = reinterpret_cast<raw*>(smem);
 
   // XCD-aware bijective remap: blocks b and b+8 share an XCD; give each XCD a contiguous tile range.
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  int tt = t;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % tiles_z;
-  const int b = tt / tiles_z;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, tiles_z);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int z0 = tz * LTD, y0 = ty * LTH, x0 = tx * LTW;
 
   // halo fill: chunk c = (row, col) with row = (hz, hy); one row is LHW contiguous voxels in HBM
@@ -582,13 +577,8 @@ __global__ __launch_bounds__(256) void conv3d_lds_pair_kernel(const ConvArgs a, 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   raw* tile = reinterpret_cast<raw*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  int tt = t;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % tiles_z;
-  const int b = tt / tiles_z;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, tiles_z);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int z0 = tz * LTD, y0 = ty * LTH, x0 = tx * LTW;
 
   const Prescale ps = ps_in<T>(a, b);
@@ -667,6 +657,42 @@ __global__ __launch_bounds__(256) void conv3d_lds_pair_kernel(const ConvArgs a, 
   am_flush<T>(a, am, b, blockIdx.x * 4 + wave);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The z-streamed kernels. Each takes its ring geometry from one of these ZRing forms (damvs_device.h) and its launcher
+// takes the dynamic LDS size and the (tx, ty, nzc) grid from the same form (launch_ztiles); what a kernel keeps in LDS
+// beyond the ring is named here too. The static_asserts pin the dynamic LDS bytes of every instantiation.
+template <typename T, int CIN, int TXG>  // stride-1 k3 layers: 8 x 16 TXG output windows, a one-voxel halo all round
+using ConvRing = ZRing<T, CIN / 8, 16 * TXG, LTH, 2>;
+template <int CIN, int RP, int TXG>      // conv0_dz_kernel: 2 RP rows, three depth waves per row pair
+using DzRing = ZRing<float, CIN / 8, 16 * TXG, 2 * RP, 2, 192 * RP>;
+template <typename T, int CIN>           // transposed layers: 8 x 16 q-columns, offsets 0 and +1 only
+using DeconvRing = ZRing<T, CIN / 8, 16, 8, 1>;
+template <typename T, int CIN, int TXG> constexpr size_t kZslideBytes = ConvRing<T, CIN, TXG>::bytes(4);
+template <typename T, int CIN, int TXG> constexpr size_t kZreuseBytes = ConvRing<T, CIN, TXG>::bytes(2);
+template <int RP, int TXG> constexpr int kDzChain = RP * TXG * 64;  // float4 per chain buffer (lane, row pair, column group)
+template <int CIN, int RP, int TXG>                                // 2 chains x 2 output-plane parities after the ring
+constexpr size_t kDzBytes = DzRing<CIN, RP, TXG>::bytes(2) + 4 * kDzChain<RP, TXG> * 16;
+constexpr int kXpairA = 9 * 128, kC16A = 27 * 64;  // A fragments in LDS after the ring, 16-byte slots: deconv_xpair<float>
+                                                   // (9 split chunks), deconv_c16<bf16, ALDS> (27 chunks)
+template <typename T> constexpr size_t kDeconvXpairBytes = DeconvRing<T, 16>::bytes(4) + (sizeof(T) == 4 ? kXpairA * 16 : 0);
+template <typename T> constexpr size_t kDeconvC16Bytes = DeconvRing<T, 32>::bytes(4) + (sizeof(T) == 2 ? kC16A * 16 : 0);
+// conv_s2_c8_zslide_kernel has its own pixel layout (17 x 33 8-channel pixels; fp32: rows of 34, hi / lo slots)
+struct S2Tile {  // its block: 8 x 16 output columns
+  static constexpr int TX = 16, TY = 8, NT = 256;
+};
+template <typename T> constexpr int kS2Slots = sizeof(T) == 2 ? 5 : 4;
+template <typename T> constexpr size_t kS2PlaneBytes = sizeof(T) == 2 ? 17 * 33 * 16 : 17 * 34 * 32;
+static_assert(kZslideBytes<bf16_t, 8, 2> == 21760 && kZslideBytes<bf16_t, 16, 2> == 43520 && kZslideBytes<bf16_t, 32, 1> == 46080);
+static_assert(kZslideBytes<float, 8, 2> == 43520 && kZslideBytes<float, 16, 1> == 46080 && kZslideBytes<float, 32, 1> == 92160);
+static_assert(kZreuseBytes<bf16_t, 8, 2> == 10880 && kZreuseBytes<bf16_t, 16, 2> == 21760 && kZreuseBytes<bf16_t, 32, 2> == 43520);
+static_assert(kZreuseBytes<float, 8, 2> == 21760 && kZreuseBytes<float, 16, 1> == 23040 && kZreuseBytes<float, 32, 1> == 46080);
+static_assert(kDzBytes<32, 4, 1> == 46080 + 16384 && kDzBytes<16, 4, 1> == 23040 + 16384 && kDzBytes<16, 2, 1> == 13824 + 8192);
+static_assert(kDzBytes<8, 4, 1> == 11520 + 16384 && kDzBytes<8, 2, 1> == 6912 + 8192);
+static_assert(kDzBytes<8, 4, 2> == 21760 + 32768 && kDzBytes<8, 2, 2> == 13056 + 16384);
+static_assert(kDeconvXpairBytes<bf16_t> == 19584 && kDeconvXpairBytes<float> == 39168 + 18432);
+static_assert(kDeconvC16Bytes<bf16_t> == 39168 + 27648 && kDeconvC16Bytes<float> == 78336);
+static_assert(kS2Slots<bf16_t> * kS2PlaneBytes<bf16_t> == 44880 && kS2Slots<float> * kS2PlaneBytes<float> == 73984);
+
 // z-sliding row-pair variant (conv0): a block owns an 8-row x TX-column output window over ZC
 // consecutive z-planes and streams the input through a 4-plane ring of (8+2) x (TX+2) x CIN halo
 // planes in LDS. Each output plane needs one new input plane, fetched into registers while the
@@ -682,21 +708,15 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 && CIN <= 8 ? 2 : 1
   typedef ZForm<T> Z;
   typedef typename Z::frag frag;
   constexpr int PL = Z::PL, ES = sizeof(T);
-  constexpr int E = 8, KC = 32, CH = CIN / E, S = CH * PL;
-  constexpr int TX = 16 * TXG, PW = TX + 2, PH = LTH + 2;
-  constexpr int PLANE = PH * PW * S;        // 16-byte slots per halo plane
-  constexpr int NLD = (PH * PW * CH + 255) / 256;  // 8-channel chunks per thread per plane
+  typedef ConvRing<T, CIN, TXG> R;
+  constexpr int E = 8, KC = 32, CH = R::CH, S = R::S, TX = R::TX, PW = R::PW, PH = R::PH, PLANE = R::PLANE, NLD = R::NLD;
   constexpr int KCHUNKS = 36 * CIN / KC;
   static_assert(KC % CIN == 0 || CIN % KC == 0, "chunking");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int x0 = tx * TX, y0 = ty * LTH, zb = tz * zc;
   const int zend = min(zb + zc, a.Do);
 
@@ -704,35 +724,8 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 && CIN <= 8 ? 2 : 1
   const Prescale ps = ps_in<T>(a, b);  // fp32: the input tensor's magnitude (damvs_device.h)
   const float wsc = ps_wscale<T>(a, ps);
   unsigned am = 0u;  // max |stored value| (fp32: the output's magnitude slot)
-  auto load_plane = [&](int iz, uint4 (*v)[PL]) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      const int row = c / (PW * CH), col = c - row * (PW * CH);
-      const int iy = y0 - 1 + row, ix = x0 - 1 + col / CH;
-      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
-                      (unsigned)ix < (unsigned)a.Wi;
-      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + x0 - 1) * CH + col) * (16u * PL);
-#pragma unroll
-      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
-    }
-  };
-  auto store_plane = [&](int iz, const uint4 (*v)[PL]) {
-    uint4* dst = ring + ((iz + 4) & 3) * PLANE;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      if (c >= PH * PW * CH) continue;
-      if constexpr (PL == 1) {
-        dst[c] = v[i][0];
-      } else {
-        const int vox = c / CH, q = c - vox * CH, sw = Z::template zsw<S>(vox % PW);
-        const F16Pair p = split8s(v[i][0], v[i][1], ps.s);
-        dst[vox * S + (q ^ sw)] = p.h;
-        dst[vox * S + ((CH + q) ^ sw)] = p.l;
-      }
-    }
-  };
+  auto load_plane = [&](int iz, uint4 (*v)[PL]) { R::load(rin, a, b, iz, y0 - 1, x0 - 1, v); };
+  auto store_plane = [&](int iz, const uint4 (*v)[PL]) { R::store(ring + ((iz + 4) & 3) * PLANE, v, ps.s); };
   // the layer's A fragments stay in registers for all ZC planes (bf16: 18 / 36 VGPR quads for CIN 16 / 32)
   frag wreg[KCHUNKS];
   {
@@ -880,22 +873,16 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? (CIN == 32 ? 1 : 
   typedef ZForm<T> Z;
   typedef typename Z::frag frag;
   constexpr int PL = Z::PL, ES = sizeof(T);
-  constexpr int E = 8, KC = 32, CH = CIN / E, S = CH * PL;
-  constexpr int TX = 16 * TXG, PW = TX + 2, PH = LTH + 2;
-  constexpr int PLANE = PH * PW * S;            // 16-byte slots per halo plane
-  constexpr int NLD = (PH * PW * CH + 255) / 256;  // 8-channel chunks per thread per plane
+  typedef ConvRing<T, CIN, TXG> R;
+  constexpr int E = 8, KC = 32, CH = R::CH, S = R::S, TX = R::TX, PW = R::PW, PH = R::PH, PLANE = R::PLANE, NLD = R::NLD;
   constexpr int KCHUNKS = 36 * CIN / KC;
   constexpr int NJ = KCHUNKS / 3;  // K chunks per kernel depth
   static_assert(KC % CIN == 0 || CIN % KC == 0, "chunking");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int x0 = tx * TX, y0 = ty * LTH, zb = tz * zc;
   const int zend = min(zb + zc, a.Do);
 
@@ -903,35 +890,9 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? (CIN == 32 ? 1 : 
   const Prescale ps = ps_in<T>(a, b);  // fp32: the input tensor's magnitude (damvs_device.h)
   const float wsc = ps_wscale<T>(a, ps);
   unsigned am = 0u;  // max |stored value| (fp32: the output's magnitude slot)
-  auto load_plane = [&](int iz, uint4 (*v)[PL]) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      const int row = c / (PW * CH), col = c - row * (PW * CH);
-      const int iy = y0 - 1 + row, ix = x0 - 1 + col / CH;
-      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
-                      (unsigned)ix < (unsigned)a.Wi;
-      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + x0 - 1) * CH + col) * (16u * PL);
-#pragma unroll
-      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
-    }
-  };
-  auto store_plane = [&](int iz, const uint4 (*v)[PL]) {
-    uint4* dst = ring + ((iz + 2) & 1) * PLANE;  // two slots: plane p + 1 goes where plane p - 1 was
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      if (c >= PH * PW * CH) continue;
-      if constexpr (PL == 1) {
-        dst[c] = v[i][0];
-      } else {
-        const int vox = c / CH, q = c - vox * CH, sw = Z::template zsw<S>(vox % PW);
-        const F16Pair p = split8s(v[i][0], v[i][1], ps.s);
-        dst[vox * S + (q ^ sw)] = p.h;
-        dst[vox * S + ((CH + q) ^ sw)] = p.l;
-      }
-    }
-  };
+  auto load_plane = [&](int iz, uint4 (*v)[PL]) { R::load(rin, a, b, iz, y0 - 1, x0 - 1, v); };
+  // two slots: plane p + 1 goes where plane p - 1 was
+  auto store_plane = [&](int iz, const uint4 (*v)[PL]) { R::store(ring + ((iz + 2) & 1) * PLANE, v, ps.s); };
   frag wreg[KCHUNKS];
   {
     const uint4* __restrict__ wsrc = reinterpret_cast<const uint4*>(PL == 1 ? a.wpack_pair : a.wpack32) + (threadIdx.x & 63);
@@ -1043,26 +1004,20 @@ __global__ __launch_bounds__(192 * RP) DAMVS_WAVES(CIN == 8 ? 4 : 3) void conv0_
     const ConvArgs a, int tiles_x, int tiles_y, int nzc, int zc, int ntiles) {
   typedef ZForm<float> Z;
   typedef Z::frag frag;
-  constexpr int PL = 2, ES = 4, NT = 192 * RP;
-  constexpr int E = 8, KC = 32, CH = CIN / E, S = CH * PL;
-  constexpr int LR = 2 * RP;  // output rows per block
-  constexpr int TX = 16 * TXG, PW = TX + 2, PH = LR + 2;
-  constexpr int PLANE = PH * PW * S;             // 16-byte slots per halo plane
-  constexpr int NLD = (PH * PW * CH + NT - 1) / NT;  // 8-channel chunks per thread per plane
+  typedef DzRing<CIN, RP, TXG> R;
+  constexpr int PL = 2, ES = 4, NT = R::NT;
+  constexpr int E = 8, KC = 32, CH = R::CH, S = R::S, TX = R::TX, PW = R::PW, PH = R::PH, PLANE = R::PLANE, NLD = R::NLD;
+  constexpr int LR = R::TY;  // output rows per block
   constexpr int KCHUNKS = 36 * CIN / KC;
   constexpr int NJ = KCHUNKS / 3;  // K chunks per kernel depth
-  constexpr int CHAIN = RP * TXG * 64;  // float4 per chain buffer (one per lane, row pair and column group)
+  constexpr int CHAIN = kDzChain<RP, TXG>;
   static_assert(KC % CIN == 0 || CIN % KC == 0, "chunking");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
   f32x4_t* chain = reinterpret_cast<f32x4_t*>(smem + 2 * PLANE * 16);  // [2 chains][2 parities][CHAIN]
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int x0 = tx * TX, y0 = ty * LR, zb = tz * zc;
   const int zend = min(zb + zc, a.Do);
 
@@ -1070,31 +1025,9 @@ __global__ __launch_bounds__(192 * RP) DAMVS_WAVES(CIN == 8 ? 4 : 3) void conv0_
   const Prescale ps = ps_in<float>(a, b);  // fp32: the input tensor's magnitude (damvs_device.h)
   const float wsc = ps_wscale<float>(a, ps);
   unsigned am = 0u;  // max |stored value| (the output's magnitude slot)
-  auto load_plane = [&](int iz, uint4 (*v)[PL]) DAMVS_INLINE {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * NT;
-      const int row = c / (PW * CH), col = c - row * (PW * CH);
-      const int iy = y0 - 1 + row, ix = x0 - 1 + col / CH;
-      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
-                      (unsigned)ix < (unsigned)a.Wi;
-      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + x0 - 1) * CH + col) * (16u * PL);
-#pragma unroll
-      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
-    }
-  };
-  auto store_plane = [&](int iz, const uint4 (*v)[PL]) DAMVS_INLINE {
-    uint4* dst = ring + ((iz + 2) & 1) * PLANE;  // two slots: plane p + 1 goes where plane p - 1 was
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * NT;
-      if (c >= PH * PW * CH) continue;
-      const int vox = c / CH, q = c - vox * CH, sw = Z::template zsw<S>(vox % PW);
-      const F16Pair pr = split8s(v[i][0], v[i][1], ps.s);
-      dst[vox * S + (q ^ sw)] = pr.h;
-      dst[vox * S + ((CH + q) ^ sw)] = pr.l;
-    }
-  };
+  auto load_plane = [&](int iz, uint4 (*v)[PL]) DAMVS_INLINE { R::load(rin, a, b, iz, y0 - 1, x0 - 1, v); };
+  // two slots: plane p + 1 goes where plane p - 1 was
+  auto store_plane = [&](int iz, const uint4 (*v)[PL]) DAMVS_INLINE { R::store(ring + ((iz + 2) & 1) * PLANE, v, ps.s); };
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int rp = wave % RP, dz = wave / RP;  // wave-uniform
   frag wreg[NJ];
@@ -1181,115 +1114,6 @@ __global__ __launch_bounds__(192 * RP) DAMVS_WAVES(CIN == 8 ? 4 : 3) void conv0_
   am_flush<float>(a, am, b, blockIdx.x * 3 * RP + wave);
 }
 
-template <int CIN, int RP, int TXG>
-hipError_t launch_dz_t(hipStream_t s, const ConvArgs& a) {
-  constexpr int PLANE = (2 * RP + 2) * (16 * TXG + 2) * (CIN / 8) * 2;
-  const size_t smem = 2 * PLANE * 16 + 4 * (size_t)RP * TXG * 64 * 16;
-  constexpr int zc = 16;
-  const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + 2 * RP - 1) / (2 * RP), nzc = (a.Do + zc - 1) / zc;
-  const long long nt = (long long)tx * ty * nzc * a.B;
-  return launch_big_lds(conv0_dz_kernel<CIN, RP, TXG>, dim3((unsigned)nt), dim3(192 * RP), smem, s, a, tx, ty, nzc, zc,
-                        (int)nt);
-}
-
-// DAMVS_CONV0_DZ (read per call): "0" = off (the input-plane walk / output-plane walk as DAMVS_CONV0_REUSE says), "1"
-// or "RP,TXG" = on at every CIN (RP,TXG: the block shape); unset: on at CIN 32 only. Measured at cfgC B = 4
-// (tools/unet_layers.py, profiles/r06/layers_conv0_dz_r06e.txt): stage 1 (CIN 32) 1.787 -> 1.665 ms; stage 2 (CIN 16)
-// 2.074 -> 2.614 ms and stage 3 (CIN 8) 1.304 -> 1.577 ms slower -- with one accumulator chain per wave (TXG 1) each
-// B fragment's three split MFMAs depend on each other, where the walk interleaves three depths' accumulators; at CIN 32
-// the three waves per SIMD (against one) cover that latency.
-bool conv0_dz_shape(int CIN, int& rp, int& txg) {
-  const char* v = switch_value(SW_CONV0_DZ);
-  rp = 4;
-  txg = CIN == 8 ? 2 : 1;
-  if (!v || !v[0]) return CIN == 32;  // unset or empty: the default
-  if (v[0] == '1' && !v[1]) return true;
-  if (v[0] == '0') return false;
-  const char* c = strchr(v, ',');
-  rp = atoi(v);
-  txg = c ? atoi(c + 1) : txg;
-  return true;
-}
-
-template <int CIN>
-hipError_t launch_dz(hipStream_t s, const ConvArgs& a, int rp, int txg) {
-  // the shapes that build without spills (tests/test_codeobj.py): CIN 32 (4, 1); CIN 16 (4, 1), (2, 1); CIN 8 all four
-  if (rp == 4 && txg == 1) return launch_dz_t<CIN, 4, 1>(s, a);
-  if constexpr (CIN <= 16) {
-    if (rp == 2 && txg == 1) return launch_dz_t<CIN, 2, 1>(s, a);
-  }
-  if constexpr (CIN == 8) {
-    if (rp == 4 && txg == 2) return launch_dz_t<CIN, 4, 2>(s, a);
-    if (rp == 2 && txg == 2) return launch_dz_t<CIN, 2, 2>(s, a);
-  }
-  return hipErrorInvalidValue;
-}
-
-template <typename T, int CIN, int TXG>
-hipError_t launch_zslide_pair_t(hipStream_t s, const ConvArgs& a) {
-  constexpr int PLANE = (LTH + 2) * (16 * TXG + 2) * (CIN / 8) * ZForm<T>::PL;
-  const size_t smem = 4 * PLANE * 16;
-  constexpr int zc = 16;  // z-planes per block; measured: 16 beats 8 and 32 over stages 1-2 at B=4
-  const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + LTH - 1) / LTH, nzc = (a.Do + zc - 1) / zc;
-  const long long nt = (long long)tx * ty * nzc * a.B;
-  return launch_big_lds(conv3d_zslide_pair_kernel<T, CIN, TXG>, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc,
-                        (int)nt);
-}
-
-// conv0 on the input-plane walk (conv3d_zreuse_pair_kernel, 2-slot ring)
-template <typename T, int CIN, int TXG>
-hipError_t launch_zreuse_pair_t(hipStream_t s, const ConvArgs& a) {
-  constexpr int PLANE = (LTH + 2) * (16 * TXG + 2) * (CIN / 8) * ZForm<T>::PL;
-  const size_t smem = 2 * PLANE * 16;
-  constexpr int zc = 16;
-  const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + LTH - 1) / LTH, nzc = (a.Do + zc - 1) / zc;
-  const long long nt = (long long)tx * ty * nzc * a.B;
-  hipLaunchKernelGGL((conv3d_zreuse_pair_kernel<T, CIN, TXG>), dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc,
-                     (int)nt);
-  return hipGetLastError();
-}
-
-template <typename T, int CIN>
-hipError_t launch_lds_pair_t(hipStream_t s, const ConvArgs& a) {
-  if constexpr (sizeof(T) == 2) {
-    if (!a.resid && !switch_on(SW_CONV_NO_ZSLIDE)) {
-      // DAMVS_CONV0_REUSE (read per call): 1 = the input-plane walk at every CIN, 0 = never; default: CIN 32 only
-      // (at CIN 8 / 16 its registers cost a wave per SIMD: stage 2 / 3 U-Net 2.09 / 1.89 -> 2.22 / 2.01 ms)
-      const char* rv = switch_value(SW_CONV0_REUSE);
-      const bool reuse = rv ? rv[0] == '1' : CIN == 32;
-      if (reuse) return launch_zreuse_pair_t<T, CIN, 2>(s, a);
-      if constexpr (CIN == 32) return launch_zslide_pair_t<T, CIN, 1>(s, a);
-      else return launch_zslide_pair_t<T, CIN, 2>(s, a);
-    }
-  } else {
-    // fp32: the split-f16 z-streamed kernel on the 32-K row-pair packing, A fragments in registers (CIN 32: 36 pairs,
-    // 288 VGPRs, with the 92 KB ring one block and one wave per SIMD)
-    if (!a.resid && a.wpack32 && !switch_on(SW_CONV_NO_ZSLIDE)) {
-      int rp, txg;
-      if (conv0_dz_shape(CIN, rp, txg)) return launch_dz<CIN>(s, a, rp, txg);
-      // DAMVS_CONV0_REUSE (read per call): 1 = the input-plane walk, 0 = the output-plane walk; default: the walk at CIN
-      // 16 / 32 (bitwise equal, test_conv0_reuse_fp32_bitwise)
-      const char* rv = switch_value(SW_CONV0_REUSE);
-      const bool reuse = rv ? rv[0] == '1' : CIN >= 16;
-      if (reuse) return launch_zreuse_pair_t<T, CIN, CIN >= 16 ? 1 : 2>(s, a);
-      if constexpr (CIN >= 16) return launch_zslide_pair_t<T, CIN, 1>(s, a);  // 8 x 16 windows, no spill
-      else return launch_zslide_pair_t<T, CIN, 2>(s, a);
-    }
-  }
-  const int tx = (a.Wo + LTW - 1) / LTW, ty = (a.Ho + LTH - 1) / LTH, tz = (a.Do + LTD - 1) / LTD;
-  const long long nt = (long long)tx * ty * tz * a.B;
-  return launch_big_lds(conv3d_lds_pair_kernel<T, CIN>, dim3((unsigned)nt), dim3(256), lds_tile_bytes<T, CIN>(), s, a, tx,
-                        ty, tz, (int)nt);
-}
-
-template <typename T, int CIN, int MT>
-hipError_t launch_lds_t(hipStream_t s, const ConvArgs& a) {
-  const int tx = (a.Wo + LTW - 1) / LTW, ty = (a.Ho + LTH - 1) / LTH, tz = (a.Do + LTD - 1) / LTD;
-  const long long nt = (long long)tx * ty * tz * a.B;
-  return launch_big_lds(conv3d_lds_kernel<T, CIN, MT>, dim3((unsigned)nt), dim3(256), lds_tile_bytes<T, CIN>(), s, a, tx,
-                        ty, tz, (int)nt);
-}
-
 // conv2 (Conv3d k3 s1 p1, 16 -> 16 channels) streamed along z on conv0's plan (4-slot ring of
 // (8+2) x (TX+2) x 16-channel planes, two planes ahead), with 16 output channels as the MFMA rows
 // instead of conv0's row pairs: K = 27 taps x 16 channels in 14 chunks of 2 taps (lane group g:
@@ -1303,19 +1127,14 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? 2 : 1) void conv_
   typedef ZForm<T> Z;
   typedef typename Z::frag frag;
   constexpr int PL = Z::PL, ES = sizeof(T);
-  constexpr int CH = 2, S = CH * PL, TX = 16 * TXG, PW = TX + 2, PH = LTH + 2;
-  constexpr int PLANE = PH * PW * S;
-  constexpr int NLD = (PH * PW * CH + 255) / 256;
+  typedef ConvRing<T, 16, TXG> R;
+  constexpr int CH = R::CH, S = R::S, TX = R::TX, PW = R::PW, PH = R::PH, PLANE = R::PLANE, NLD = R::NLD;
   constexpr int KCH = 14;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int x0 = tx * TX, y0 = ty * LTH, zb = tz * zc;
   const int zend = min(zb + zc, a.Do);
 
@@ -1323,35 +1142,8 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? 2 : 1) void conv_
   const Prescale ps = ps_in<T>(a, b);  // fp32: the input tensor's magnitude (damvs_device.h)
   const float wsc = ps_wscale<T>(a, ps);
   unsigned am = 0u;  // max |stored value| (fp32: the output's magnitude slot)
-  auto load_plane = [&](int iz, uint4 (*v)[PL]) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      const int row = c / (PW * CH), col = c - row * (PW * CH);
-      const int iy = y0 - 1 + row, ix = x0 - 1 + col / CH;
-      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
-                      (unsigned)ix < (unsigned)a.Wi;
-      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + x0 - 1) * CH + col) * (16u * PL);
-#pragma unroll
-      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
-    }
-  };
-  auto store_plane = [&](int iz, const uint4 (*v)[PL]) {
-    uint4* dst = ring + ((iz + 4) & 3) * PLANE;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      if (c >= PH * PW * CH) continue;
-      if constexpr (PL == 1) {
-        dst[c] = v[i][0];
-      } else {
-        const int vox = c / CH, q = c - vox * CH, sw = Z::template zsw<S>(vox % PW);
-        const F16Pair p = split8s(v[i][0], v[i][1], ps.s);
-        dst[vox * S + (q ^ sw)] = p.h;
-        dst[vox * S + ((CH + q) ^ sw)] = p.l;
-      }
-    }
-  };
+  auto load_plane = [&](int iz, uint4 (*v)[PL]) { R::load(rin, a, b, iz, y0 - 1, x0 - 1, v); };
+  auto store_plane = [&](int iz, const uint4 (*v)[PL]) { R::store(ring + ((iz + 4) & 3) * PLANE, v, ps.s); };
   frag wreg[KCH];
   {
     const uint4* __restrict__ wsrc = reinterpret_cast<const uint4*>(PL == 1 ? a.wpack : a.wpack32) + (threadIdx.x & 63);
@@ -1431,37 +1223,6 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 4 ? 2 : 1) void conv_
   am_flush<T>(a, am, b, blockIdx.x * 4 + wave);
 }
 
-// Returns hipErrorNotSupported when no LDS variant fits this layer (caller falls back).
-template <typename T>
-hipError_t launch_lds(hipStream_t s, const ConvArgs& a) {
-  if (a.nphase != 1 || a.in_stride != 1 || a.out_stride != 1 || a.ph[0].ntaps != 27) return hipErrorNotSupported;
-  const int MT = a.MT;
-  if (a.wpack_pair && a.Cout <= 8) {
-    if (a.Cin == 8) return launch_lds_pair_t<T, 8>(s, a);
-    if (a.Cin == 16) return launch_lds_pair_t<T, 16>(s, a);
-    if (a.Cin == 32) return launch_lds_pair_t<T, 32>(s, a);  // fp32: the 138 KB tile (one block per CU)
-  }
-  if ((sizeof(T) == 2 || a.wpack32) && a.Cin == 16 && a.Cout == 16 && MT == 1 && !a.resid && !switch_on(SW_CONV_NO_ZSLIDE)) {
-    constexpr int zc = 16, TXG = sizeof(T) == 2 ? 2 : 1;
-    const int tx = (a.Wo + 16 * TXG - 1) / (16 * TXG), ty = (a.Ho + LTH - 1) / LTH, nzc = (a.Do + zc - 1) / zc;
-    const long long nt = (long long)tx * ty * nzc * a.B;
-    const size_t smem = 4 * (LTH + 2) * (16 * TXG + 2) * 2 * 16 * ZForm<T>::PL;
-    hipLaunchKernelGGL((conv_s1_c16_zslide_kernel<T, TXG>), dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc,
-                       (int)nt);
-    return hipGetLastError();
-  }
-  // The 4 x 8 x 16 tile stages a 6-plane halo: with fewer than 4 output planes (the deep levels at D = 8) most of
-  // it is padding, and at 64 channels (conv6) it takes 138 KB of LDS (one block per CU). Measured (B=4, bf16)
-  // the gather kernel wins both: conv6 98 -> 64 us (stage 2), 165 -> 53 us (stage 3); conv4 at stage 3 (2
-  // planes) 137 -> 117 us, while conv4 at stage 2 (8 planes) keeps the tile (93 against 137 us).
-  if (a.Do < LTD || a.Cin >= 64) return hipErrorNotSupported;
-  if (a.Cin == 8 && MT == 1) return launch_lds_t<T, 8, 1>(s, a);
-  if (a.Cin == 16 && MT == 1) return launch_lds_t<T, 16, 1>(s, a);
-  if (a.Cin == 32 && MT == 1) return launch_lds_t<T, 32, 1>(s, a);
-  if (a.Cin == 32 && MT == 2) return launch_lds_t<T, 32, 2>(s, a);
-  return hipErrorNotSupported;
-}
-
 // conv11 (ConvTranspose3d k3 s2 p1 op1, 16 -> 8 channels, in-place skip) streamed along z:
 // a block owns 8 x 16 input-grid columns (q) over DZ consecutive q-planes; input planes pass
 // through a 4-slot LDS ring ((8+1) x (16+1) x 16 channels: the deconv only reaches offsets 0 and
@@ -1477,18 +1238,13 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 2 ? 3 : 2) void decon
   typedef ZForm<T> Z;
   typedef typename Z::frag frag;
   constexpr int PL = Z::PL, ES = sizeof(T);
-  constexpr int CH = 2, S = CH * PL, QX = 16, QY = 8, PW = QX + 1, PH = QY + 1;
-  constexpr int PLANE = PH * PW * S;           // 16-byte slots per ring plane
-  constexpr int NLD = (PH * PW * CH + 255) / 256;  // 8-channel chunks per thread per plane
+  typedef DeconvRing<T, 16> R;
+  constexpr int CH = R::CH, S = R::S, QX = R::TX, QY = R::TY, PW = R::PW, PH = R::PH, PLANE = R::PLANE, NLD = R::NLD;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int qx0 = tx * QX, qy0 = ty * QY, zb = tz * zc;
   const int zend = min(zb + zc, a.Di);
 
@@ -1496,47 +1252,20 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(sizeof(T) == 2 ? 3 : 2) void decon
   const Prescale ps = ps_in<T>(a, b);  // fp32: the input tensor's magnitude (damvs_device.h)
   const float wsc = ps_wscale<T>(a, ps);
   unsigned am = 0u;  // max |stored value| (fp32: the output's magnitude slot)
-  auto load_plane = [&](int iz, uint4 (*v)[PL]) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      const int row = c / (PW * CH), col = c - row * (PW * CH);
-      const int iy = qy0 + row, ix = qx0 + col / CH;
-      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
-                      (unsigned)ix < (unsigned)a.Wi;
-      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + qx0) * CH + col) * (16u * PL);
-#pragma unroll
-      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
-    }
-  };
-  auto store_plane = [&](int iz, const uint4 (*v)[PL]) {
-    uint4* dst = ring + (iz & 3) * PLANE;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      if (c >= PH * PW * CH) continue;
-      if constexpr (PL == 1) {
-        dst[c] = v[i][0];
-      } else {
-        const int vox = c / CH, q = c - vox * CH, sw = Z::template zsw<S>(vox % PW);
-        const F16Pair p = split8s(v[i][0], v[i][1], ps.s);
-        dst[vox * S + (q ^ sw)] = p.h;
-        dst[vox * S + ((CH + q) ^ sw)] = p.l;
-      }
-    }
-  };
+  auto load_plane = [&](int iz, uint4 (*v)[PL]) { R::load(rin, a, b, iz, qy0, qx0, v); };
+  auto store_plane = [&](int iz, const uint4 (*v)[PL]) { R::store(ring + (iz & 3) * PLANE, v, ps.s); };
   // A fragments: bf16 in registers (9 x 4 VGPRs); fp32 (split, twice the registers) in LDS after the ring, read per
   // use, so the kernel keeps two waves per SIMD
   constexpr int NWR = PL == 1 ? 9 : 1;
   frag wreg[NWR];
-  uint4* alds = ring + 4 * PLANE;  // fp32: 9 chunks x 128 slots
+  uint4* alds = ring + 4 * PLANE;  // fp32: kXpairA slots (9 chunks x 128)
   if constexpr (PL == 1) {
     const uint4* __restrict__ wsrc = reinterpret_cast<const uint4*>(a.wpack) + (threadIdx.x & 63);
 #pragma unroll
     for (int s = 0; s < 9; ++s) wreg[s] = Z::wload(wsrc, s, 0);
   } else {
     const uint4* __restrict__ wsrc = reinterpret_cast<const uint4*>(a.wpack);
-    for (int i = threadIdx.x; i < 9 * 128; i += 256) alds[i] = wsrc[i];
+    for (int i = threadIdx.x; i < kXpairA; i += 256) alds[i] = wsrc[i];
   }
   auto wfrag = [&](int s) -> frag {
     if constexpr (PL == 1) return wreg[s];
@@ -1660,19 +1389,14 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(ALDS ? 2 : 1) void deconv_c16_zsli
   typedef ZForm<T> Z;
   typedef typename Z::frag frag;
   constexpr int PL = Z::PL, ES = sizeof(T);
-  constexpr int CH = 4, S = CH * PL, QX = 16, QY = 8, PW = QX + 1, PH = QY + 1;
-  constexpr int PLANE = PH * PW * S;
-  constexpr int NLD = (PH * PW * CH + 255) / 256;
+  typedef DeconvRing<T, 32> R;
+  constexpr int CH = R::CH, S = R::S, QX = R::TX, QY = R::TY, PW = R::PW, PH = R::PH, PLANE = R::PLANE, NLD = R::NLD;
   static_assert(!ALDS || PL == 1, "A fragments in LDS: bf16 form");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int qx0 = tx * QX, qy0 = ty * QY, zb = tz * zc;
   const int zend = min(zb + zc, a.Di);
 
@@ -1680,40 +1404,13 @@ __global__ __launch_bounds__(256) DAMVS_WAVES(ALDS ? 2 : 1) void deconv_c16_zsli
   const Prescale ps = ps_in<T>(a, b);  // fp32: the input tensor's magnitude (damvs_device.h)
   const float wsc = ps_wscale<T>(a, ps);
   unsigned am = 0u;  // max |stored value| (fp32: the output's magnitude slot)
-  auto load_plane = [&](int iz, uint4 (*v)[PL]) {
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      const int row = c / (PW * CH), col = c - row * (PW * CH);
-      const int iy = qy0 + row, ix = qx0 + col / CH;
-      const bool ok = c < PH * PW * CH && (unsigned)iz < (unsigned)a.Di && (unsigned)iy < (unsigned)a.Hi &&
-                      (unsigned)ix < (unsigned)a.Wi;
-      const uint32_t off = (uint32_t)((((b * a.Di + iz) * a.Hi + iy) * a.Wi + qx0) * CH + col) * (16u * PL);
-#pragma unroll
-      for (int h = 0; h < PL; ++h) v[i][h] = BufIO<bf16_t>::frag(rin, ok ? off + 16u * h : kOOB);
-    }
-  };
-  auto store_plane = [&](int iz, const uint4 (*v)[PL]) {
-    uint4* dst = ring + (iz & 3) * PLANE;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const int c = threadIdx.x + i * 256;
-      if (c >= PH * PW * CH) continue;
-      if constexpr (PL == 1) {
-        dst[c] = v[i][0];
-      } else {
-        const int vox = c / CH, q = c - vox * CH, sw = Z::template zsw<S>(vox % PW);
-        const F16Pair p = split8s(v[i][0], v[i][1], ps.s);
-        dst[vox * S + (q ^ sw)] = p.h;
-        dst[vox * S + ((CH + q) ^ sw)] = p.l;
-      }
-    }
-  };
+  auto load_plane = [&](int iz, uint4 (*v)[PL]) { R::load(rin, a, b, iz, qy0, qx0, v); };
+  auto store_plane = [&](int iz, const uint4 (*v)[PL]) { R::store(ring + (iz & 3) * PLANE, v, ps.s); };
   frag wreg[ALDS ? 1 : 27];
   uint4* aw = ring + 4 * PLANE;
   if constexpr (ALDS) {
     const uint4* __restrict__ wsrc = reinterpret_cast<const uint4*>(a.wpack);
-    for (int i = threadIdx.x; i < 27 * 64; i += 256) aw[i] = wsrc[i];
+    for (int i = threadIdx.x; i < kC16A; i += 256) aw[i] = wsrc[i];
   } else {
     const uint4* __restrict__ wsrc = reinterpret_cast<const uint4*>(PL == 1 ? a.wpack : a.wpack32) + (threadIdx.x & 63);
 #pragma unroll
@@ -1857,7 +1554,7 @@ __global__ __launch_bounds__(256) void conv_s2_c8_zslide_kernel(const ConvArgs a
   typedef ZForm<T> Z;
   typedef typename Z::frag frag;
   constexpr int PL = Z::PL, ES = sizeof(T);
-  constexpr int QX = 16, QY = 8, PW = 2 * QX + 1, PH = 2 * QY + 1;
+  constexpr int QX = S2Tile::TX, QY = S2Tile::TY, PW = 2 * QX + 1, PH = 2 * QY + 1;
   constexpr int HCE = (PW + 1) / 2, PWE = PL == 1 ? PW : 2 * HCE;  // fp32: even / odd column halves of a row
   constexpr int NPIX = PH * PW;         // 8-channel pixels per halo plane
   constexpr int PLANE = PH * PWE * PL;  // 16-byte slots per ring plane
@@ -1865,16 +1562,13 @@ __global__ __launch_bounds__(256) void conv_s2_c8_zslide_kernel(const ConvArgs a
   // ring slots: bf16 5 (planes 2z - 1 .. 2z + 3: the next two planes stored after the MFMAs, one barrier per plane);
   // fp32 4 (74 KB instead of 92: two blocks per CU instead of one), plane 2z + 3 then goes into the slot of 2z - 1
   // behind a second barrier
-  constexpr int NS = PL == 1 ? 5 : 4;
+  constexpr int NS = kS2Slots<T>;
+  static_assert(PLANE * 16 == kS2PlaneBytes<T>, "the launcher's plane");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);
 
-  const int bid = blockIdx.x, q8 = ntiles / 8, r8 = ntiles % 8, xcd = bid % 8;
-  int tt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
-  const int tx = tt % tiles_x; tt /= tiles_x;
-  const int ty = tt % tiles_y; tt /= tiles_y;
-  const int tz = tt % nzc;
-  const int b = tt / nzc;
+  const Tile4 tl4 = tile4_of(blockIdx.x, ntiles, tiles_x, tiles_y, nzc);
+  const int tx = tl4.tx, ty = tl4.ty, tz = tl4.tz, b = tl4.b;
   const int ox0 = tx * QX, oy0 = ty * QY, zb = tz * zc;
   const int zend = min(zb + zc, a.Do);
   const int ix0 = 2 * ox0 - 1, iy0 = 2 * oy0 - 1;
@@ -1998,93 +1692,229 @@ __global__ __launch_bounds__(256) void conv_s2_c8_zslide_kernel(const ConvArgs a
   am_flush<T>(a, am, b, blockIdx.x * 4 + wave);
 }
 
-template <typename T>
-hipError_t launch_t(hipStream_t s, const ConvArgs& a) {
-  long long Qtot = (long long)a.B * a.Dq * a.Hq * a.Wq;
-  long long per_block = 4LL * kGroups * 16;
+// ---------------------------------------------------------------------------------------------
+// Routing: conv3d_route decides a layer's kernel once and without a HIP call, launch_route runs it.
+enum class Conv3dFamily {
+  invalid,
+  zreuse_pair, zslide_pair, dz, lds_pair,  // the row-pair packing (conv0 of every stage)
+  c16_zslide, tile,                        // the other one-phase stride-1 27-tap layers
+  deconv_xpair_zslide, s2_c8_zslide, deconv_c16_zslide,
+  xpair_gather, gather32, gather,          // conv3d_mfma_kernel (gather32: fp32 on the wgat32 packing)
+};
+struct Conv3dRoute {
+  Conv3dFamily family;
+  bool per_sample;  // one batch element per launch
+  int cin;          // the row-pair families, tile: the kernel's CIN
+  int mt;           // tile, gather32, gather: 16-channel output tiles per wave
+  int rp, txg;      // dz: the block shape
+};
+
+// a: the layer; store: ST_BF16 / ST_F32. The order of precedence:
+//  1. operands of 2 GiB or more (32-bit device offsets) run one batch element per launch; a single element that large
+//     is invalid
+//  2. one-phase stride-1 27-tap layers with the row-pair packing at Cin 8 / 16 / 32 end here: the z-streamed kernels
+//     (bf16: the input-plane walk or the output-plane walk; fp32 on wpack32: dz, else the walk or the output-plane
+//     walk), and with a residual, under DAMVS_CONV_NO_ZSLIDE or at fp32 without wpack32 conv3d_lds_pair_kernel
+//  3. the 16 -> 16 z-streamed kernel
+//  4. fewer than LTD output planes, or Cin >= 64: off to the gather kernel (6 on)
+//  5. the 4 x 8 x 16 tile kernel
+//  6. the transposed / stride-2 z-streamed kernels
+//  7. fp32 magnitude slots on a q-grid smaller than a wave's 64 voxels: one batch element per launch
+//  8. the x-pair gather, 9. the 32-K gather, 10. the 16-K gather
+Conv3dRoute conv3d_route(const ConvArgs& a, int store) {
+  const bool bf16 = store == ST_BF16;
+  Conv3dRoute r = {};
+  auto is = [&r](Conv3dFamily f) {
+    r.family = f;
+    return r;
+  };
+  const long long lim = 1LL << 31, es = bf16 ? 2 : 4;
+  const long long in_b = (long long)a.Di * a.Hi * a.Wi * a.Cin * es, out_b = (long long)a.Do * a.Ho * a.Wo * a.Cout * es;
+  if (in_b >= lim || out_b >= lim) return is(Conv3dFamily::invalid);
+  r.per_sample = a.B > 1 && (in_b * a.B >= lim || out_b * a.B >= lim);
+  r.cin = a.Cin;
+  r.mt = a.MT;
+  const bool w32 = bf16 || a.wpack32;  // fp32 z-streamed kernels run on the layer's 32-K split packing
+  if (a.nphase == 1 && a.in_stride == 1 && a.out_stride == 1 && a.ph[0].ntaps == 27) {
+    const bool zslide = w32 && !a.resid && !switch_on(SW_CONV_NO_ZSLIDE);
+    if (a.wpack_pair && a.Cout <= 8 && (a.Cin == 8 || a.Cin == 16 || a.Cin == 32)) {
+      if (!zslide) return is(Conv3dFamily::lds_pair);  // (fp32 at Cin 32: the 138 KB tile, one block per CU)
+      if (!bf16) {
+        // DAMVS_CONV0_DZ: "0" = off, "1" or "RP,TXG" = on at every Cin (RP,TXG: the block shape; launch_route has the
+        // shapes that build without spills); unset or empty: on at Cin 32 only. Measured at cfgC B = 4
+        // (tools/unet_layers.py, profiles/r06/layers_conv0_dz_r06e.txt): stage 1 (Cin 32) 1.787 -> 1.665 ms; stage 2
+        // (Cin 16) 2.074 -> 2.614 ms and stage 3 (Cin 8) 1.304 -> 1.577 ms slower -- with one accumulator chain per
+        // wave (TXG 1) each B fragment's three split MFMAs depend on each other, where the walk interleaves three
+        // depths' accumulators; at Cin 32 the three waves per SIMD (against one) cover that latency.
+        const char* v = switch_value(SW_CONV0_DZ);
+        r.rp = 4;
+        r.txg = a.Cin == 8 ? 2 : 1;
+        const bool set = v && v[0];
+        if (set && v[0] != '0' && !(v[0] == '1' && !v[1])) {
+          const char* c = strchr(v, ',');
+          r.rp = atoi(v);
+          r.txg = c ? atoi(c + 1) : r.txg;
+        }
+        if (set ? v[0] != '0' : a.Cin == 32) return is(Conv3dFamily::dz);
+      }
+      // DAMVS_CONV0_REUSE: 1 = the input-plane walk at every Cin, anything else = the output-plane walk; default: the
+      // walk at bf16 Cin 32 (at Cin 8 / 16 its registers cost a wave per SIMD: stage 2 / 3 U-Net 2.09 / 1.89 -> 2.22 /
+      // 2.01 ms) and at fp32 Cin 16 / 32 (bitwise equal, test_conv0_reuse_fp32_bitwise)
+      const char* rv = switch_value(SW_CONV0_REUSE);
+      const bool reuse = rv ? rv[0] == '1' : a.Cin >= (bf16 ? 32 : 16);
+      return is(reuse ? Conv3dFamily::zreuse_pair : Conv3dFamily::zslide_pair);
+    }
+    if (zslide && a.Cin == 16 && a.Cout == 16 && a.MT == 1) return is(Conv3dFamily::c16_zslide);
+    // The 4 x 8 x 16 tile stages a 6-plane halo: with fewer than 4 output planes (the deep levels at D = 8) most of
+    // it is padding, and at 64 channels (conv6) it takes 138 KB of LDS (one block per CU). Measured (B=4, bf16)
+    // the gather kernel wins both: conv6 98 -> 64 us (stage 2), 165 -> 53 us (stage 3); conv4 at stage 3 (2
+    // planes) 137 -> 117 us, while conv4 at stage 2 (8 planes) keeps the tile (93 against 137 us).
+    if (a.Do >= LTD && a.Cin < 64 &&
+        (((a.Cin == 8 || a.Cin == 16 || a.Cin == 32) && a.MT == 1) || (a.Cin == 32 && a.MT == 2)))
+      return is(Conv3dFamily::tile);
+  }
+  if (w32 && !switch_on(SW_DECONV_NO_ZSLIDE)) {
+    if (a.xpair && a.Cin == 16 && a.Cout == 8 && a.nphase == 4) return is(Conv3dFamily::deconv_xpair_zslide);
+    if (a.nphase == 1 && a.in_stride == 2 && a.Cin == 8 && a.Cout == 16 && a.MT == 1 && !a.resid && a.ph[0].ntaps == 27)
+      return is(Conv3dFamily::s2_c8_zslide);
+    if (!a.xpair && a.nphase == 8 && a.Cin == 32 && a.Cout == 16 && a.MT == 1) return is(Conv3dFamily::deconv_c16_zslide);
+  }
+  // the gather kernel's waves straddle at most two batch elements (per-voxel prescales); a q-grid of fewer voxels
+  // than a wave runs one batch element per launch
+  if (!bf16 && a.B > 1 && (a.in_amax || a.out_amax) && a.Dq * a.Hq * a.Wq < kGroups * 16) r.per_sample = true;
+  if (a.xpair) return is(a.MT == 1 && a.Cout == 8 ? Conv3dFamily::xpair_gather : Conv3dFamily::invalid);
+  if (a.MT != 1 && a.MT != 2 && a.MT != 4) return is(Conv3dFamily::invalid);
+  // fp32: the 32-K split form where the layer has its packing (DAMVS_CONV3D_K16=1: the 16-K form)
+  return is(!bf16 && a.wgat32 && !switch_on(SW_CONV3D_K16) ? Conv3dFamily::gather32 : Conv3dFamily::gather);
+}
+
+// batch element b of a layer as a layer of its own (its tensors, its magnitude slots)
+ConvArgs sample_args(const ConvArgs& a, int b, long long es) {
+  const long long in_b = (long long)a.Di * a.Hi * a.Wi * a.Cin * es, out_b = (long long)a.Do * a.Ho * a.Wo * a.Cout * es;
+  ConvArgs a1 = a;
+  a1.B = 1;
+  a1.in = static_cast<const char*>(a.in) + b * in_b;
+  a1.out = static_cast<char*>(a.out) + b * out_b;
+  a1.resid = a.resid ? static_cast<const char*>(a.resid) + b * out_b : nullptr;
+  a1.in_amax = a.in_amax ? a.in_amax + (size_t)b * kAmaxSlotWords : nullptr;
+  a1.out_amax = a.out_amax ? a.out_amax + (size_t)b * kAmaxSlotWords : nullptr;
+  return a1;
+}
+
+// A z-streamed kernel on ring form R: one block per R::TX x R::TY columns and zc planes of the (W, H, D) grid it walks
+template <typename R, typename... P>
+hipError_t launch_ztiles(void (*k)(P...), size_t smem, int zc, int W, int H, int D, hipStream_t s, const ConvArgs& a) {
+  const int tx = (W + R::TX - 1) / R::TX, ty = (H + R::TY - 1) / R::TY, nzc = (D + zc - 1) / zc;
+  const long long nt = (long long)tx * ty * nzc * a.B;
+  return launch_big_lds(k, dim3((unsigned)nt), dim3(R::NT), smem, s, a, tx, ty, nzc, zc, (int)nt);
+}
+// conv3d_lds_kernel / conv3d_lds_pair_kernel: one block per 4 x 8 x 16 output tile
+template <typename T, int CIN, typename... P>
+hipError_t launch_tile(void (*k)(P...), hipStream_t s, const ConvArgs& a) {
+  const int tx = (a.Wo + LTW - 1) / LTW, ty = (a.Ho + LTH - 1) / LTH, tz = (a.Do + LTD - 1) / LTD;
+  const long long nt = (long long)tx * ty * tz * a.B;
+  return launch_big_lds(k, dim3((unsigned)nt), dim3(256), lds_tile_bytes<T, CIN>(), s, a, tx, ty, tz, (int)nt);
+}
+template <typename T, bool XP, bool K32>
+hipError_t launch_gather(hipStream_t s, const ConvArgs& a, int mt) {
+  const long long Qtot = (long long)a.B * a.Dq * a.Hq * a.Wq, per_block = 4LL * kGroups * 16;
   const int nq = (int)((Qtot + per_block - 1) / per_block);
-  dim3 grid((unsigned)(nq * a.nphase));
-  const bool zslide = !switch_on(SW_DECONV_NO_ZSLIDE);  // read per call: tests flip it between launches
-  if ((sizeof(T) == 2 || a.wpack32) && a.xpair && a.Cin == 16 && a.Cout == 8 && a.nphase == 4 && zslide) {
-    constexpr int zc = 8;
-    const int tx = (a.Wi + 15) / 16, ty = (a.Hi + 7) / 8, nzc = (a.Di + zc - 1) / zc;
-    const long long nt = (long long)tx * ty * nzc * a.B;
-    const size_t smem = 4 * 9 * 17 * 2 * 16 * ZForm<T>::PL + (sizeof(T) == 4 ? 9 * 128 * 16 : 0);
-    ConvArgs az = a;
-    if (sizeof(T) == 4) az.wpack = a.wpack32;  // fp32: the blocked 32-K split packing of the x-pair phases
-    hipLaunchKernelGGL(deconv_xpair_zslide_kernel<T>, dim3((unsigned)nt), dim3(256), smem, s, az, tx, ty, nzc, zc, (int)nt);
-    return hipGetLastError();
-  }
-  if ((sizeof(T) == 2 || a.wpack32) && a.nphase == 1 && a.in_stride == 2 && a.Cin == 8 && a.Cout == 16 && a.MT == 1 &&
-      !a.resid && a.ph[0].ntaps == 27 && zslide) {
-    constexpr int zc = 8;
-    const int tx = (a.Wo + 15) / 16, ty = (a.Ho + 7) / 8, nzc = (a.Do + zc - 1) / zc;
-    const long long nt = (long long)tx * ty * nzc * a.B;
-    const size_t smem = sizeof(T) == 2 ? 5 * 17 * 33 * 16 : 4 * 17 * 34 * 32;  // ring slots (NS) x plane
-    return launch_big_lds(conv_s2_c8_zslide_kernel<T>, dim3((unsigned)nt), dim3(256), smem, s, a, tx, ty, nzc, zc, (int)nt);
-  }
-  if ((sizeof(T) == 2 || a.wpack32) && !a.xpair && a.nphase == 8 && a.Cin == 32 && a.Cout == 16 && a.MT == 1 && zslide) {
-    constexpr int zc = 8;
-    const int tx = (a.Wi + 15) / 16, ty = (a.Hi + 7) / 8, nzc = (a.Di + zc - 1) / zc;
-    const long long nt = (long long)tx * ty * nzc * a.B;
-    const size_t ring = 4 * 9 * 17 * 4 * 16 * ZForm<T>::PL;
-    if constexpr (sizeof(T) == 2) {
-      // the A fragments in LDS (27 KB) instead of 108 VGPRs: two waves per SIMD instead of one, U-Net 1.136-1.149 /
-      // 2.071-2.102 / 1.879-1.884 -> 1.128-1.129 / 2.020-2.024 / 1.826-1.837 ms (profiles/r03/ab_conv9.jsonl)
-      hipLaunchKernelGGL((deconv_c16_zslide_kernel<T, true>), dim3((unsigned)nt), dim3(256), ring + 27 * 64 * 16, s, a,
-                         tx, ty, nzc, zc, (int)nt);
-      return hipGetLastError();
-    } else {  // the fp32 ring is 78,336 bytes
-      return launch_big_lds(deconv_c16_zslide_kernel<T, false>, dim3((unsigned)nt), dim3(256), ring, s, a, tx, ty, nzc, zc,
-                            (int)nt);
-    }
-  }
-  if (sizeof(T) == 4 && a.B > 1 && (a.in_amax || a.out_amax) && a.Dq * a.Hq * a.Wq < kGroups * 16) {
-    // the gather kernel's waves straddle at most two batch elements (per-voxel prescales); a q-grid of fewer voxels
-    // than a wave runs one batch element per launch
-    const long long in_b = (long long)a.Di * a.Hi * a.Wi * a.Cin * 4, out_b = (long long)a.Do * a.Ho * a.Wo * a.Cout * 4;
-    for (int b = 0; b < a.B; ++b) {
-      ConvArgs a1 = a;
-      a1.B = 1;
-      a1.in = static_cast<const char*>(a.in) + b * in_b;
-      a1.out = static_cast<char*>(a.out) + b * out_b;
-      a1.resid = a.resid ? static_cast<const char*>(a.resid) + b * out_b : nullptr;
-      a1.in_amax = a.in_amax ? a.in_amax + (size_t)b * kAmaxSlotWords : nullptr;
-      a1.out_amax = a.out_amax ? a.out_amax + (size_t)b * kAmaxSlotWords : nullptr;
-      const hipError_t e = launch_t<T>(s, a1);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  if (a.xpair) {
-    if (a.MT != 1 || a.Cout != 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv3d_mfma_kernel<T, 1, true>), grid, dim3(256), 0, s, a, nq);
-    return hipGetLastError();
-  }
-  if constexpr (sizeof(T) == 4) {
-    // fp32: the 32-K split form where the layer has its packing (DAMVS_CONV3D_K16=1, read per call: the 16-K form)
-    if (a.wgat32 && !switch_on(SW_CONV3D_K16)) {
-      ConvArgs a2 = a;
-      for (int p = 0; p < a.nphase; ++p) {  // the phases of the 32-K packing (LayerPlan, build_phases(., 32))
-        a2.ph[p].kchunks = a.k32_chunks[p];
-        a2.ph[p].w_off = a.k32_off[p];
-      }
-      switch (a.MT) {
-        case 1: hipLaunchKernelGGL((conv3d_mfma_kernel<T, 1, false, true>), grid, dim3(256), 0, s, a2, nq); break;
-        case 2: hipLaunchKernelGGL((conv3d_mfma_kernel<T, 2, false, true>), grid, dim3(256), 0, s, a2, nq); break;
-        case 4: hipLaunchKernelGGL((conv3d_mfma_kernel<T, 4, false, true>), grid, dim3(256), 0, s, a2, nq); break;
-        default: return hipErrorInvalidValue;
-      }
-      return hipGetLastError();
-    }
-  }
-  switch (a.MT) {
-    case 1: hipLaunchKernelGGL((conv3d_mfma_kernel<T, 1, false>), grid, dim3(256), 0, s, a, nq); break;
-    case 2: hipLaunchKernelGGL((conv3d_mfma_kernel<T, 2, false>), grid, dim3(256), 0, s, a, nq); break;
-    case 4: hipLaunchKernelGGL((conv3d_mfma_kernel<T, 4, false>), grid, dim3(256), 0, s, a, nq); break;
-    default: return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(nq * a.nphase));
+  if (XP || mt == 1) hipLaunchKernelGGL((conv3d_mfma_kernel<T, 1, XP, K32>), grid, dim3(256), 0, s, a, nq);
+  if constexpr (!XP) {
+    if (mt == 2) hipLaunchKernelGGL((conv3d_mfma_kernel<T, 2, false, K32>), grid, dim3(256), 0, s, a, nq);
+    if (mt == 4) hipLaunchKernelGGL((conv3d_mfma_kernel<T, 4, false, K32>), grid, dim3(256), 0, s, a, nq);
   }
   return hipGetLastError();
+}
+template <int N> using IntC = std::integral_constant<int, N>;
+template <typename F>
+hipError_t with_cin(int cin, F f) {  // f(IntC<CIN>()) at CIN 8 / 16 / 32
+  if (cin == 8) return f(IntC<8>());
+  if (cin == 16) return f(IntC<16>());
+  return cin == 32 ? f(IntC<32>()) : hipErrorInvalidValue;
+}
+
+template <typename T>
+hipError_t launch_route(hipStream_t s, const Conv3dRoute& r, const ConvArgs& a) {
+  constexpr bool bf16 = sizeof(T) == 2;
+  switch (r.family) {
+    case Conv3dFamily::zreuse_pair:  // bf16: 8 x 32 windows; fp32: 8 x 16 at CIN 16 / 32
+      return with_cin(r.cin, [&](auto c) {
+        constexpr int CIN = decltype(c)::value, TXG = bf16 || CIN == 8 ? 2 : 1;
+        return launch_ztiles<ConvRing<T, CIN, TXG>>(conv3d_zreuse_pair_kernel<T, CIN, TXG>, kZreuseBytes<T, CIN, TXG>, 16,
+                                                    a.Wo, a.Ho, a.Do, s, a);
+      });
+    case Conv3dFamily::zslide_pair:  // 8 x 32 windows; 8 x 16 at bf16 CIN 32 and fp32 CIN 16 / 32 (no spill)
+      return with_cin(r.cin, [&](auto c) {  // zc 16: measured, beats 8 and 32 over stages 1-2 at B = 4
+        constexpr int CIN = decltype(c)::value, TXG = CIN == 8 || (bf16 && CIN == 16) ? 2 : 1;
+        return launch_ztiles<ConvRing<T, CIN, TXG>>(conv3d_zslide_pair_kernel<T, CIN, TXG>, kZslideBytes<T, CIN, TXG>, 16,
+                                                    a.Wo, a.Ho, a.Do, s, a);
+      });
+    case Conv3dFamily::dz:
+      if constexpr (!bf16) {
+        return with_cin(r.cin, [&](auto c) {
+          constexpr int CIN = decltype(c)::value;
+          auto go = [&](auto rp, auto txg) {
+            constexpr int RP = decltype(rp)::value, TXG = decltype(txg)::value;
+            return launch_ztiles<DzRing<CIN, RP, TXG>>(conv0_dz_kernel<CIN, RP, TXG>, kDzBytes<CIN, RP, TXG>, 16, a.Wo,
+                                                       a.Ho, a.Do, s, a);
+          };
+          // the shapes that build without spills (tests/test_codeobj.py): CIN 32 (4, 1); CIN 16 (4, 1), (2, 1); CIN 8 all four
+          if (r.rp == 4 && r.txg == 1) return go(IntC<4>(), IntC<1>());
+          if constexpr (CIN <= 16) {
+            if (r.rp == 2 && r.txg == 1) return go(IntC<2>(), IntC<1>());
+          }
+          if constexpr (CIN == 8) {
+            if (r.rp == 4 && r.txg == 2) return go(IntC<4>(), IntC<2>());
+            if (r.rp == 2 && r.txg == 2) return go(IntC<2>(), IntC<2>());
+          }
+          return hipErrorInvalidValue;
+        });
+      }
+      break;
+    case Conv3dFamily::lds_pair:
+      return with_cin(r.cin, [&](auto c) {
+        constexpr int CIN = decltype(c)::value;
+        return launch_tile<T, CIN>(conv3d_lds_pair_kernel<T, CIN>, s, a);
+      });
+    case Conv3dFamily::c16_zslide: {  // bf16 8 x 32 windows; fp32 8 x 16, so the 14 split A pairs fit two waves per SIMD
+      constexpr int TXG = bf16 ? 2 : 1;
+      return launch_ztiles<ConvRing<T, 16, TXG>>(conv_s1_c16_zslide_kernel<T, TXG>, kZslideBytes<T, 16, TXG>, 16, a.Wo, a.Ho,
+                                                 a.Do, s, a);
+    }
+    case Conv3dFamily::tile:
+      if (r.mt == 2) return launch_tile<T, 32>(conv3d_lds_kernel<T, 32, 2>, s, a);
+      return with_cin(r.cin, [&](auto c) {
+        constexpr int CIN = decltype(c)::value;
+        return launch_tile<T, CIN>(conv3d_lds_kernel<T, CIN, 1>, s, a);
+      });
+    case Conv3dFamily::deconv_xpair_zslide: {
+      ConvArgs az = a;
+      if (!bf16) az.wpack = a.wpack32;  // fp32: the blocked 32-K split packing of the x-pair phases
+      return launch_ztiles<DeconvRing<T, 16>>(deconv_xpair_zslide_kernel<T>, kDeconvXpairBytes<T>, 8, a.Wi, a.Hi, a.Di, s, az);
+    }
+    case Conv3dFamily::s2_c8_zslide:
+      return launch_ztiles<S2Tile>(conv_s2_c8_zslide_kernel<T>, kS2Slots<T> * kS2PlaneBytes<T>, 8, a.Wo, a.Ho, a.Do, s, a);
+    case Conv3dFamily::deconv_c16_zslide:
+      // bf16: the A fragments in LDS (27 KB) instead of 108 VGPRs: two waves per SIMD instead of one, U-Net 1.136-1.149 /
+      // 2.071-2.102 / 1.879-1.884 -> 1.128-1.129 / 2.020-2.024 / 1.826-1.837 ms (profiles/r03/ab_conv9.jsonl)
+      return launch_ztiles<DeconvRing<T, 32>>(deconv_c16_zslide_kernel<T, bf16>, kDeconvC16Bytes<T>, 8, a.Wi, a.Hi, a.Di, s, a);
+    case Conv3dFamily::xpair_gather: return launch_gather<T, true, false>(s, a, 1);
+    case Conv3dFamily::gather32:
+      if constexpr (!bf16) {
+        ConvArgs a2 = a;
+        for (int p = 0; p < a.nphase; ++p) {  // the phases of the 32-K packing (LayerPlan, build_phases(., 32))
+          a2.ph[p].kchunks = a.k32_chunks[p];
+          a2.ph[p].w_off = a.k32_off[p];
+        }
+        return launch_gather<T, false, true>(s, a2, r.mt);
+      }
+      break;
+    case Conv3dFamily::gather: return launch_gather<T, false, false>(s, a, r.mt);
+    case Conv3dFamily::invalid: break;
+  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -2094,27 +1924,16 @@ hipError_t launch_conv3d(hipStream_t s, int store, const ConvArgs& a0) {
   a.div_wq = make_fastdiv(a.Wq);
   a.div_hq = make_fastdiv(a.Hq);
   a.div_dq = make_fastdiv(a.Dq);
-  // 32-bit device offsets: operands of 2 GiB or more run one batch element per launch
-  const long long es = store == ST_BF16 ? 2 : 4;
-  const long long in_b = (long long)a.Di * a.Hi * a.Wi * a.Cin * es, out_b = (long long)a.Do * a.Ho * a.Wo * a.Cout * es;
-  if (a.B > 1 && (in_b * a.B >= (1LL << 31) || out_b * a.B >= (1LL << 31))) {
-    for (int b = 0; b < a.B; ++b) {
-      ConvArgs a1 = a0;
-      a1.B = 1;
-      a1.in = static_cast<const char*>(a0.in) + b * in_b;
-      a1.out = static_cast<char*>(a0.out) + b * out_b;
-      a1.resid = a0.resid ? static_cast<const char*>(a0.resid) + b * out_b : nullptr;
-      a1.in_amax = a0.in_amax ? a0.in_amax + (size_t)b * kAmaxSlotWords : nullptr;  // per-sample magnitude slots
-      a1.out_amax = a0.out_amax ? a0.out_amax + (size_t)b * kAmaxSlotWords : nullptr;
-      const hipError_t e = launch_conv3d(s, store, a1);
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+  const Conv3dRoute r = conv3d_route(a, store);
+  auto run = [&](const ConvArgs& x) {
+    return store == ST_BF16 ? launch_route<bf16_t>(s, r, x) : launch_route<float>(s, r, x);
+  };
+  if (!r.per_sample) return run(a);
+  for (int b = 0; b < a.B; ++b) {
+    const hipError_t e = run(sample_args(a, b, store == ST_BF16 ? 2 : 4));
+    if (e != hipSuccess) return e;
   }
-  if (in_b >= (1LL << 31) || out_b >= (1LL << 31)) return hipErrorInvalidValue;
-  const hipError_t e = store == ST_BF16 ? launch_lds<bf16_t>(s, a) : launch_lds<float>(s, a);
-  if (e != hipErrorNotSupported) return e;
-  return store == ST_BF16 ? launch_t<bf16_t>(s, a) : launch_t<float>(s, a);
+  return hipSuccess;
 }
 
 }  // namespace damvs

@@ -189,8 +189,7 @@ __global__ __launch_bounds__(256) void conv2d_planes_mfma_kernel(const Conv2dArg
   // logical block = (column of tiles, group of nt tile rows, image), XCD-contiguous; the group's tiles run in turn
   const int tgroups = (tiles_y + nt - 1) / nt;
   const int nblk = tiles_x * tgroups * a.B;
-  const int bid = blockIdx.x, q8 = nblk / 8, r8 = nblk % 8, xcd = bid % 8;
-  const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + bid / 8;
+  const int L = xcd_block(blockIdx.x, nblk);
   const int tx = L % tiles_x, tg = (L / tiles_x) % tgroups, b = L / (tiles_x * tgroups);
   const int x0 = tx * TC, ty0 = tg * nt, ty1 = min(ty0 + nt, tiles_y);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
