@@ -74,8 +74,8 @@ struct damvs_stage {
   int C = 0, base = 0, mode = 0, dtype = 0, device = 0;
   LayerPlan L[10];
   float* prob_w = nullptr;  // device [kd][kh][kw][c]
-  void* prob_pack = nullptr;  // bf16, base 8: banded MFMA form of the prob conv (pack_prob_banded)
-  void* prob_split = nullptr;  // fp32, base 8: the same rows as split-f16 pairs (the fused head, k_head.hip)
+  void* prob_pack = nullptr;  // bf16, base 8: prob_mfma_kernel's A operand (pack_prob_rows, damvs_stage_create)
+  void* prob_split = nullptr;  // fp32, base 8: the same rows as split-f16 pairs (prob_mfma_kernel<float>)
   float prob_scale = 1.f;      // 2^-k of prob_split
   float k1[32] = {0};
   float s1 = 0, t1 = 0, s2 = 0, t2 = 0;
@@ -472,20 +472,14 @@ WarpArgs warp_args(const damvs_stage* st, int B, int N, int C, int D, int h, int
 // (models/cas_mvsnet.py:105-124) on the U-Net output c0 [B][D][h][w][base].
 int regress_tail(const damvs_stage* st, hipStream_t s, int B, int D, int h, int w, const void* feat, const float* hyps,
                  const float* prob_init, float* logits, float* depth, float* conf, float* var, float* prob) {
-  // base 8: the prob conv on MFMA (logits in an LDS column, as the VALU kernel below); fp32 as split-f16 MFMAs
-  const void* pk = st->dtype == DAMVS_BF16 ? st->prob_pack : st->prob_split;
-  if (pk && prob_mfma_smem(st->dtype, D) <= 160 * 1024 && prob_mfma_enabled(st->dtype))
-    return hip_check(launch_prob_mfma(s, st->dtype, B, D, h, w, feat, pk, st->dtype == DAMVS_BF16 ? 1.f : st->prob_scale,
-                                      prob_init, hyps, depth, conf, var, prob),
-                     "prob_mfma launch");
-  if (prob_regress_smem_bytes(st->dtype, st->base, D) <= 160 * 1024)  // fused: logits stay in LDS
-    return hip_check(launch_prob_regress(s, st->dtype, B, st->base, D, h, w, feat, st->prob_w, prob_init, hyps, depth,
-                                         conf, var, prob),
-                     "prob_regress launch");
-  if (!logits) return fail(DAMVS_E_WORKSPACE, "this D needs the logits scratch buffer");
-  DAMVS_TRY(hip_check(launch_prob_conv(s, st->dtype, B, st->base, D, h, w, feat, st->prob_w, prob_init, logits),
-                      "prob conv launch"));
-  return hip_check(launch_regress(s, B, D, h, w, logits, hyps, depth, conf, var, prob), "regress launch");
+  // base 8: the stage's MFMA packing for its storage type (fp32: split-f16 rows and their 2^-k); k_regress.hip routes
+  const bool bf16 = st->dtype == DAMVS_BF16;
+  const TailArgs a = {B, st->base, D, h, w, feat, st->prob_w, bf16 ? st->prob_pack : st->prob_split,
+                      bf16 ? 1.f : st->prob_scale, prob_init, hyps, logits, depth, conf, var, prob};
+  const char* what = nullptr;
+  const hipError_t e = launch_tail(s, st->dtype, a, &what);
+  if (e != hipSuccess && !what) return fail(DAMVS_E_WORKSPACE, "this D needs the logits scratch buffer");
+  return hip_check(e, what);
 }
 
 // U-Net layer i (conv0..conv6, conv7, conv9, conv11): (input level, output level)

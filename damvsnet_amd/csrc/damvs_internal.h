@@ -194,25 +194,33 @@ struct FusionArgs {
 };
 hipError_t launch_fusion_view(hipStream_t s, const FusionArgs& a);
 
+// ---------------------------------------------------------------- stage tail (k_regress.hip)
+// prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
+// fp32 prob-conv weight (hi + lo)
+constexpr int kProbRowChunks = 5, kProbRowTerms = 2;
+// The prob conv alone (first pass of the two-pass tail; damvs_costreg_logits): logits (+ prob_init) to HBM.
+// hipErrorInvalidValue for a base other than 8 or 16.
 hipError_t launch_prob_conv(hipStream_t s, int store, int B, int Cb, int D, int h, int w, const void* feat,
                             const float* wprob, const float* prob_init, float* logits);
-hipError_t launch_prob_regress(hipStream_t s, int store, int B, int Cb, int D, int h, int w, const void* feat,
-                               const float* wprob, const float* prob_init, const float* hyps, float* depth,
-                               float* conf, float* var, float* prob);
-size_t prob_regress_smem_bytes(int store, int Cb, int D);
-// MFMA prob conv + regression (bf16 storage, base 8; LDS bounds D): apack from pack_prob_rows (capi.cpp)
-#ifndef DAMVS_PROB_TERMS
-#define DAMVS_PROB_TERMS 2  // bf16 terms per fp32 prob-conv weight (3: exact fp32 weights; A/B builds)
-#endif
-constexpr int kProbRowChunks = 5, kProbRowTerms = DAMVS_PROB_TERMS;  // prob_mfma_kernel: 18 voxel slots x 8 channels
-// store ST_F32: the split-f16 form (apack = damvs_stage prob_split, pscale its 2^-k)
-hipError_t launch_prob_mfma(hipStream_t s, int store, int B, int D, int h, int w, const void* feat, const void* apack,
-                            float pscale, const float* prob_init, const float* hyps, float* depth, float* conf,
-                            float* var, float* prob);
-size_t prob_mfma_smem(int store, int D);
-bool prob_mfma_enabled(int store);  // bf16 unless DAMVS_PROB_MFMA=0; fp32 only with DAMVS_PROB_MFMA=1
+// The regression alone, from logits in HBM (second pass of the two-pass tail; damvs_regress).
 hipError_t launch_regress(hipStream_t s, int B, int D, int h, int w, const float* logits, const float* hyps,
                           float* depth, float* conf, float* var, float* prob);
+// A stage's prob conv + regression on the form tail_route picks. apack: the stage's MFMA packing for its storage type
+// (bf16: prob_pack; fp32: prob_split with pscale its 2^-k), or nullptr; logits: scratch of the two-pass form.
+// Returns the first failing launch's error with *what its hip_check label. A two-pass route without logits launches
+// nothing and returns an error with *what = nullptr (the caller's DAMVS_E_WORKSPACE).
+struct TailArgs {
+  int B, Cb, D, h, w;
+  const void* feat;     // [B][D][h][w][Cb], storage type
+  const float* wprob;   // [kd][kh][kw][Cb]
+  const void* apack;
+  float pscale;
+  const float* prob_init;
+  const float* hyps;
+  float* logits;
+  float *depth, *conf, *var, *prob;  // prob may be nullptr
+};
+hipError_t launch_tail(hipStream_t s, int store, const TailArgs& a, const char** what);
 
 #ifdef __HIPCC__
 // Launch a kernel whose dynamic LDS may exceed the 64 KB a kernel gets without asking: above that, raise the kernel's

@@ -1,18 +1,22 @@
-// Final probability conv + depth regression.
+// The tail of a stage: final probability conv + depth regression.
 //
-//  prob_conv : CostRegNet.prob, Conv3d(base, 1, k3, p1, bias=False) (models/module.py:530,540).
-//              One thread per pixel column (b, y, x) slides over the D planes: each input plane's
-//              3x3 x Cb neighbourhood is loaded once and contributes to logits d-1, d, d+1
-//              (3x fewer loads than a per-output gather). Optional prob_volume_init is added
-//              (models/cas_mvsnet.py:107-108).
+//  prob conv : CostRegNet.prob, Conv3d(base, 1, k3, p1, bias=False) (models/module.py:530,540) on the U-Net output
+//              [B][D][h][w][base]; prob_volume_init is added to the logits (models/cas_mvsnet.py:107-108).
 //  regress   : softmax over D (:110), depth = sum p*d (module.py:609-615), photometric
 //              confidence = sum of p over [i*-1, i*+2] at i* = clamp(long(sum p*i), 0, D-1)
 //              (:113-118, the 4*avg_pool3d of the padded volume), exp-variance
 //              3*sqrt(sum (d - depth)^2 p) (:121-124); optional prob volume write.
-#include <cstdlib>
-#include <type_traits>
-
+//
+// Kernels (a 256-thread block owns an 8 x 32 pixel tile for all D planes in each conv form):
+//  prob_mfma_kernel<T>               conv on the matrix cores + regression, logits in an LDS column (base 8)
+//  prob_regress_kernel<T, CB, false> conv on the VALU + regression, logits in an LDS column
+//  prob_regress_kernel<T, CB, true>  the same conv alone, logits (+ prob_init) to HBM: first pass of the two-pass
+//                                    form and damvs_costreg_logits
+//  regress_kernel                    regression from logits in HBM: second pass, and damvs_regress
+//  finite_check_kernel, amax_kernel  the range check of a stage's outputs; max |x| of a tensor
+// tail_route picks the form of a stage's tail, launch_tail runs it (below the kernels).
 #include <algorithm>
+#include <type_traits>
 
 #include "damvs_device.h"
 
@@ -20,55 +24,90 @@ namespace damvs {
 
 namespace {
 
-template <typename T, int CB>
-__global__ __launch_bounds__(256) void prob_conv_kernel(int B, int D, int h, int w, const T* __restrict__ feat,
-                                                        const float* __restrict__ wprob,
-                                                        const float* __restrict__ prob_init,
-                                                        float* __restrict__ logits) {
-  const float* sw = wprob;  // [kd][kh][kw][c], wave-uniform -> scalar loads
-  const int hw = h * w;
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  const int b = blockIdx.y;
-  if (p >= hw) return;
-  const int y = p / w, x = p - y * w;
-  float am1 = 0.f, a0 = 0.f;  // partial logits for d = plane-1 (after this plane) and d = plane+1
-  for (int pl = 0; pl < D; ++pl) {
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f;  // kd = 0 -> d = pl+1, kd = 1 -> d = pl, kd = 2 -> d = pl-1
+// The regression of one pixel (models/cas_mvsnet.py:110-124) over its column of D logits, prob_init already added:
+// max, e = expf(l - mx) summed, p = e / sum, depth and index sums, then variance and the window sum, every sum in
+// plane order. Col is where the column lives:
+//   logit(d)            the logit of plane d
+//   keep(d, e)          e = expf(logit(d) - mx) has been formed
+//   prob(d, mx, sum)    p of plane d, first use; again(d, mx, sum): every later use
+// out(d, p) receives each probability once. Hypotheses (hy, plane stride hw) are loaded in groups of 8 ahead of their
+// use (one memory latency per group, not per plane); D is any value >= 1.
+struct Regressed {
+  float depth, conf, var;
+};
+
+template <typename Col, typename Out>
+__device__ __forceinline__ Regressed regress_column(Col& col, int D, const float* __restrict__ hy, size_t hw, Out&& out) {
+  float mx = -INFINITY;
+  for (int d = 0; d < D; ++d) mx = fmaxf(mx, col.logit(d));
+  float sum = 0.f;
+  for (int d = 0; d < D; ++d) {
+    const float e = expf(col.logit(d) - mx);
+    col.keep(d, e);
+    sum += e;
+  }
+  float dep = 0.f, idx = 0.f;
+  for (int d0 = 0; d0 < D; d0 += 8) {
+    float hv[8];
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) {
-      const int yy = y + ky - 1;
-      if (yy < 0 || yy >= h) continue;
+    for (int i = 0; i < 8; ++i) hv[i] = d0 + i < D ? hy[(size_t)(d0 + i) * hw] : 0.f;
 #pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const int xx = x + kx - 1;
-        if (xx < 0 || xx >= w) continue;
-        float v[CB];
-        load_vec<T, CB>(feat + ((((size_t)b * D + pl) * h + yy) * w + xx) * CB, v);
-        // wave-uniform weights through the scalar cache (SGPR operands of v_fmac)
-        const float* w0 = wprob + ((0 * 3 + ky) * 3 + kx) * CB;
-        const float* w1 = wprob + ((1 * 3 + ky) * 3 + kx) * CB;
-        const float* w2 = wprob + ((2 * 3 + ky) * 3 + kx) * CB;
-#pragma unroll
-        for (int c = 0; c < CB; ++c) {
-          c0 += w0[c] * v[c];
-          c1 += w1[c] * v[c];
-          c2 += w2[c] * v[c];
-        }
+    for (int i = 0; i < 8; ++i) {
+      const int d = d0 + i;
+      if (d < D) {
+        const float pr = col.prob(d, mx, sum);
+        dep += pr * hv[i];
+        idx += pr * (float)d;
       }
     }
-    float* lo = logits + ((size_t)b * D) * hw + p;
-    if (pl >= 1) {
-      float l = am1 + c2;
-      if (prob_init) l += prob_init[((size_t)b * D + pl - 1) * hw + p];
-      lo[(size_t)(pl - 1) * hw] = l;
-    }
-    am1 = a0 + c1;
-    a0 = c0;
   }
-  float l = am1;
-  if (prob_init) l += prob_init[((size_t)b * D + D - 1) * hw + p];
-  logits[((size_t)b * D + D - 1) * hw + p] = l;
+  int ii = (int)idx;  // .long() truncation; idx >= 0
+  ii = ii < 0 ? 0 : (ii > D - 1 ? D - 1 : ii);
+  float c = 0.f, vs = 0.f;
+  for (int d0 = 0; d0 < D; d0 += 8) {
+    float hv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) hv[i] = d0 + i < D ? hy[(size_t)(d0 + i) * hw] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int d = d0 + i;
+      if (d < D) {
+        const float pr = col.again(d, mx, sum);
+        const float df = hv[i] - dep;
+        vs += df * df * pr;
+        if (d >= ii - 1 && d <= ii + 2) c += pr;
+        out(d, pr);
+      }
+    }
+  }
+  return {dep, c, 3.f * sqrtf(vs)};
 }
+
+// The column of the fused kernels: rows of an LDS column at stride 256 with plane D - 1 in a register, overwritten
+// first with e and then with p.
+struct StoredColumn {
+  float* lcol;
+  float last;
+  int D;
+  __device__ __forceinline__ float& at(int d) { return d == D - 1 ? last : lcol[d * 256]; }
+  __device__ __forceinline__ void add(const float* __restrict__ pin, size_t hw) {  // prob_init (+ its plane stride)
+    for (int d = 0; d < D; ++d) at(d) += pin[(size_t)d * hw];
+  }
+  __device__ __forceinline__ float logit(int d) { return at(d); }
+  __device__ __forceinline__ void keep(int d, float e) { at(d) = e; }
+  __device__ __forceinline__ float prob(int d, float, float sum) { return at(d) = at(d) / sum; }
+  __device__ __forceinline__ float again(int d, float, float) { return at(d); }
+};
+
+// The column of regress_kernel: logits in HBM (the caller's, read only), nothing kept, p re-evaluated at every use.
+struct RecomputedColumn {
+  const float* __restrict__ lg;
+  size_t hw;
+  __device__ __forceinline__ float logit(int d) const { return lg[(size_t)d * hw]; }
+  __device__ __forceinline__ void keep(int, float) const {}
+  __device__ __forceinline__ float prob(int d, float mx, float sum) const { return expf(logit(d) - mx) / sum; }
+  __device__ __forceinline__ float again(int d, float mx, float sum) const { return prob(d, mx, sum); }
+};
 
 __global__ __launch_bounds__(256) void regress_kernel(int B, int D, int hw, const float* __restrict__ logits,
                                                       const float* __restrict__ hyps, float* __restrict__ depth,
@@ -77,44 +116,25 @@ __global__ __launch_bounds__(256) void regress_kernel(int B, int D, int hw, cons
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (p >= hw) return;
-  const float* lg = logits + (size_t)b * D * hw + p;
-  const float* hy = hyps + (size_t)b * D * hw + p;
-  float mx = -INFINITY;
-  for (int d = 0; d < D; ++d) mx = fmaxf(mx, lg[(size_t)d * hw]);
-  float sum = 0.f;
-  for (int d = 0; d < D; ++d) sum += expf(lg[(size_t)d * hw] - mx);
-  float dep = 0.f, idx = 0.f;
-  for (int d = 0; d < D; ++d) {
-    const float pr = expf(lg[(size_t)d * hw] - mx) / sum;
-    dep += pr * hy[(size_t)d * hw];
-    idx += pr * (float)d;
-    if (prob) prob[((size_t)b * D + d) * hw + p] = pr;
-  }
-  int ii = (int)idx;  // .long() truncation; idx >= 0
-  ii = ii < 0 ? 0 : (ii > D - 1 ? D - 1 : ii);
-  float c = 0.f, vs = 0.f;
-  for (int d = 0; d < D; ++d) {
-    const float pr = expf(lg[(size_t)d * hw] - mx) / sum;
-    const float df = hy[(size_t)d * hw] - dep;
-    vs += df * df * pr;
-    if (d >= ii - 1 && d <= ii + 2) c += pr;
-  }
-  depth[(size_t)b * hw + p] = dep;
-  conf[(size_t)b * hw + p] = c;
-  var[(size_t)b * hw + p] = 3.f * sqrtf(vs);
+  RecomputedColumn col{logits + (size_t)b * D * hw + p, (size_t)hw};
+  float* po = prob ? prob + (size_t)b * D * hw + p : nullptr;
+  const Regressed r = regress_column(col, D, hyps + (size_t)b * D * hw + p, (size_t)hw, [&](int d, float pr) {
+    if (po) po[(size_t)d * hw] = pr;
+  });
+  depth[(size_t)b * hw + p] = r.depth;
+  conf[(size_t)b * hw + p] = r.conf;
+  var[(size_t)b * hw + p] = r.var;
 }
 
 // Fused prob conv + regression. One 256-thread block owns an 8 x 32 pixel tile for all D planes:
 // each input plane's (8+2) x (32+2) x Cb halo tile is staged once in LDS as fp32 (double-buffered, one
 // barrier per plane, next plane's global loads issued before this plane's FMAs; bf16 is widened once
 // per voxel at staging, not once per tap), every thread slides its 3x3x3 window over the planes keeping
-// the two open logits in registers, completed logits go to an LDS column [D][256] and the regression
+// the two open logits in registers, completed logits go to an LDS column [D - 1][256] and the regression
 // runs from there. Logits never reach HBM. The channel sums run as fp32 FMAs (even / odd channel partial sums, added
-// at the end of the plane; packed FMAs until round 6, the same operations) with the 72 weights of one kernel row as
-// scalar operands
-// (the ky loop is not unrolled: all 216 weights at once would spill to VGPR lanes).
+// at the end of the plane) with the 72 weights of one kernel row as scalar operands (the ky loop is not unrolled: all
+// 216 weights at once would spill to VGPR lanes).
 constexpr int kTY = 8, kTX = 32, kHY = kTY + 2, kHX = kTX + 2;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 // TWO: first pass of the two-pass form — the same LDS-tiled prob conv, logits (+prob_init) written
 // to HBM ([B][D][h][w], argument `prob`) for regress_kernel; LDS then holds only the plane tiles, so
@@ -244,46 +264,18 @@ __global__ __launch_bounds__(256) void prob_regress_kernel(int B, int D, int h, 
     }
     return;
   }
-  float last = am1;  // plane D - 1
-
   const int y = y0 + ty, x = x0 + tx;
   if (y >= h || x >= w) return;
   const size_t hw = (size_t)h * w, pix = (size_t)y * w + x;
-  const float* hy = hyps + (size_t)b * D * hw + pix;
-  const float* pin = prob_init ? prob_init + (size_t)b * D * hw + pix : nullptr;
-  float* lcol = lg + tid;
-  auto col = [&](int d) -> float& { return d == D - 1 ? last : lcol[d * 256]; };
-  if (pin)
-    for (int d = 0; d < D; ++d) col(d) += pin[(size_t)d * hw];
-  float mx = -INFINITY;
-  for (int d = 0; d < D; ++d) mx = fmaxf(mx, col(d));
-  float sum = 0.f;
-  for (int d = 0; d < D; ++d) {
-    const float e = expf(col(d) - mx);
-    col(d) = e;
-    sum += e;
-  }
-  float dep = 0.f, idx = 0.f;
-  for (int d = 0; d < D; ++d) {
-    const float pr = col(d) / sum;
-    col(d) = pr;
-    dep += pr * hy[(size_t)d * hw];
-    idx += pr * (float)d;
-  }
-  int ii = (int)idx;
-  ii = ii < 0 ? 0 : (ii > D - 1 ? D - 1 : ii);
-  float c = 0.f, vs = 0.f;
+  StoredColumn col{lg + tid, am1, D};  // am1: plane D - 1
+  if (prob_init) col.add(prob_init + (size_t)b * D * hw + pix, hw);
   float* po = prob ? prob + (size_t)b * D * hw + pix : nullptr;
-  for (int d = 0; d < D; ++d) {
-    const float pr = col(d);
-    const float df = hy[(size_t)d * hw] - dep;
-    vs += df * df * pr;
-    if (d >= ii - 1 && d <= ii + 2) c += pr;
+  const Regressed r = regress_column(col, D, hyps + (size_t)b * D * hw + pix, hw, [&](int d, float pr) {
     if (po) po[(size_t)d * hw] = pr;
-  }
-  depth[(size_t)b * hw + pix] = dep;
-  conf[(size_t)b * hw + pix] = c;
-  var[(size_t)b * hw + pix] = 3.f * sqrtf(vs);
+  });
+  depth[(size_t)b * hw + pix] = r.depth;
+  conf[(size_t)b * hw + pix] = r.conf;
+  var[(size_t)b * hw + pix] = r.var;
 }
 
 // Prob conv on MFMA + regression (bf16 storage, 8 channels). A block owns an 8 x 32 pixel tile for all D planes,
@@ -298,7 +290,7 @@ __global__ __launch_bounds__(256) void prob_regress_kernel(int B, int D, int h, 
 // Lane group g of a B fragment is one slot = one 16-byte voxel read from LDS (16 lanes: 256 contiguous bytes).
 // The fp32 weights enter as two bf16 terms (hi + lo: ~16 mantissa bits, a relative weight error below 2^-17, far
 // under the 2^-9 rounding of the bf16 activations they multiply; bf16 x bf16 products are exact). Three terms
-// (DAMVS_PROB_TERMS=3: 24 bits, the fp32 conv up to summation order) cost the kernel its fourth wave per SIMD:
+// (kProbRowTerms = 3: 24 bits, the fp32 conv up to summation order) cost the kernel its fourth wave per SIMD:
 // stage 3 0.50 against 0.42 ms at B=4 (tools/gpu_r03_probab.sh). Lane (n, g) then holds rows 4g .. 4g+3 = pixel row g,
 // column n, partial logits of kernel depth 0, 1, 2: exactly the three sums prob_regress_kernel slides over the
 // planes; the same lane keeps its pixel's two open logits and later runs that pixel's regression from the LDS
@@ -306,10 +298,7 @@ __global__ __launch_bounds__(256) void prob_regress_kernel(int B, int D, int h, 
 // packed FMAs per voxel).
 constexpr int kPRChunks = kProbRowChunks, kPRTerms = kProbRowTerms;
 constexpr int kPRVox = kHY * kHX;  // 340 staged voxels per plane
-#ifndef DAMVS_PROB_AHEAD
-#define DAMVS_PROB_AHEAD 4  // (A/B builds only)
-#endif
-constexpr int kPRAhead = DAMVS_PROB_AHEAD;  // input planes in flight per block
+constexpr int kPRAhead = 4;        // input planes in flight per block
 
 // T = float (the fp32 path): the same plan on split-f16 MFMAs (damvs_device.h mma_split32): each staged fp32 voxel
 // (32 bytes, two loads) is split into its f16 hi / lo halves at the LDS write (two planes of 340 slots), the weights
@@ -440,69 +429,22 @@ __global__ __launch_bounds__(256) void prob_mfma_kernel(int B, int D, int h, int
       __syncthreads();
     }
   }
-  float last = am1;  // plane D - 1
-
   const int y = y0 + R0 + g, x = x0 + C0 + n;
   const size_t hw = (size_t)h * w, p = (size_t)y * w + x;
   // w % 4 == 0: the probabilities go out as 16-byte runs of 4 pixels of a tile row from the LDS column (below)
   // instead of one 4-byte store per pixel and plane
   const bool vec = prob && vec_ok;
   if (y < h && x < w) {
-  const float* hy = hyps + (size_t)b * D * hw + p;
-  const float* pin = prob_init ? prob_init + (size_t)b * D * hw + p : nullptr;
-  float* lcol = lg + pix;
-  auto col = [&](int d) -> float& { return d == D - 1 ? last : lcol[d * 256]; };
-  if (pin)
-    for (int d = 0; d < D; ++d) col(d) += pin[(size_t)d * hw];
-  float mx = -INFINITY;
-  for (int d = 0; d < D; ++d) mx = fmaxf(mx, col(d));
-  float sm = 0.f;
-  for (int d = 0; d < D; ++d) {
-    const float e = expf(col(d) - mx);
-    col(d) = e;
-    sm += e;
-  }
-  // hypothesis loads in groups of 8 ahead of their use (one memory latency per group, not per plane)
-  float dep = 0.f, idx = 0.f;
-  for (int d0 = 0; d0 < D; d0 += 8) {
-    float hv[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hv[i] = d0 + i < D ? hy[(size_t)(d0 + i) * hw] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int d = d0 + i;
-      if (d < D) {
-        const float pr = col(d) / sm;
-        col(d) = pr;
-        dep += pr * hv[i];
-        idx += pr * (float)d;
-      }
-    }
-  }
-  int ii = (int)idx;
-  ii = ii < 0 ? 0 : (ii > D - 1 ? D - 1 : ii);
-  float c = 0.f, vs = 0.f;
-  float* po = prob && !vec ? prob + (size_t)b * D * hw + p : nullptr;
-  for (int d0 = 0; d0 < D; d0 += 8) {
-    float hv[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) hv[i] = d0 + i < D ? hy[(size_t)(d0 + i) * hw] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int d = d0 + i;
-      if (d < D) {
-        const float pr = col(d);
-        const float df = hv[i] - dep;
-        vs += df * df * pr;
-        if (d >= ii - 1 && d <= ii + 2) c += pr;
-        if (po) po[(size_t)d * hw] = pr;
-      }
-    }
-  }
-  if (vec) lg[(D - 1) * 256 + pix] = last;  // the column's last plane
-  depth[(size_t)b * hw + p] = dep;
-  conf[(size_t)b * hw + p] = c;
-  var[(size_t)b * hw + p] = 3.f * sqrtf(vs);
+    StoredColumn col{lg + pix, am1, D};  // am1: plane D - 1
+    if (prob_init) col.add(prob_init + (size_t)b * D * hw + p, hw);
+    float* po = prob && !vec ? prob + (size_t)b * D * hw + p : nullptr;
+    const Regressed r = regress_column(col, D, hyps + (size_t)b * D * hw + p, hw, [&](int d, float pr) {
+      if (po) po[(size_t)d * hw] = pr;
+    });
+    if (vec) lg[(D - 1) * 256 + pix] = col.last;  // the column's last plane
+    depth[(size_t)b * hw + p] = r.depth;
+    conf[(size_t)b * hw + p] = r.conf;
+    var[(size_t)b * hw + p] = r.var;
   }
   if (vec) {
     __syncthreads();  // every pixel's normalised column is in LDS
@@ -516,71 +458,117 @@ __global__ __launch_bounds__(256) void prob_mfma_kernel(int B, int D, int h, int
   }
 }
 
-template <typename T, int CB>
-size_t prob_regress_smem(int D) {
-  return 2 * (size_t)kHY * kHX * CB * 4 + (size_t)(D > 0 ? D - 1 : 0) * 256 * 4;  // fp32 plane tiles + logit column
+
+// ---------------------------------------------------------------------------------------------
+// Routing: tail_route decides the form of a stage's tail once and without a HIP call, launch_tail runs it.
+constexpr size_t kLdsLimit = 160 * 1024;  // dynamic LDS a block may ask for
+
+// 32-bit device offsets: the bytes a kernel addresses from one base pointer stay below 2 GiB
+bool fits_offsets32(long long bytes) { return bytes < (1LL << 31); }
+
+dim3 tile_grid(int B, int h, int w) { return dim3((w + kTX - 1) / kTX, (h + kTY - 1) / kTY, B); }
+
+// LDS bytes: the two plane tiles (prob_regress_kernel: fp32, Cb channels; prob_mfma_kernel: raw 16-byte pieces) and
+// `rows` rows of the [rows][256] logit column (prob_regress_kernel D - 1, its first-pass form 0, prob_mfma_kernel D)
+size_t prob_regress_smem(int Cb, int rows) { return 2 * (size_t)kHY * kHX * Cb * 4 + (size_t)rows * 256 * 4; }
+size_t prob_mfma_smem(int store, int rows) {
+  return 2 * (size_t)kPRVox * 16 * (store == ST_BF16 ? 1 : 2) + (size_t)rows * 256 * 4;
 }
 
-template <typename T, int CB>
-hipError_t launch_pr_t(hipStream_t s, int B, int D, int h, int w, const void* feat, const float* wprob,
-                       const float* prob_init, const float* hyps, float* depth, float* conf, float* var, float* prob) {
-  const size_t smem = prob_regress_smem<T, CB>(D);
-  if (smem > 160 * 1024) return hipErrorInvalidValue;
-  if ((long long)D * h * w * CB * (long long)sizeof(T) >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit offsets
-  dim3 grid((w + kTX - 1) / kTX, (h + kTY - 1) / kTY, B);
-  return launch_big_lds(prob_regress_kernel<T, CB, false>, grid, dim3(256), smem, s, B, D, h, w,
-                        reinterpret_cast<const T*>(feat), wprob, prob_init, hyps, depth, conf, var, prob);
+// f(T{}, integral_constant<int, CB>{}) for the storage type and base of a stage; a base other than 8 or 16 is invalid
+template <typename F>
+hipError_t for_store_base(int store, int Cb, F&& f) {
+  using C8 = std::integral_constant<int, 8>;
+  using C16 = std::integral_constant<int, 16>;
+  if (Cb == 8) return store == ST_BF16 ? f(bf16_t{}, C8{}) : f(float{}, C8{});
+  if (Cb == 16) return store == ST_BF16 ? f(bf16_t{}, C16{}) : f(float{}, C16{});
+  return hipErrorInvalidValue;
 }
 
-template <typename T, int CB>
-hipError_t launch_pc_lds(hipStream_t s, int B, int D, int h, int w, const void* feat, const float* wprob,
-                         const float* prob_init, float* logits) {
-  const size_t smem = prob_regress_smem<T, CB>(0);
-  if ((long long)D * h * w * CB * (long long)sizeof(T) >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit offsets
-  dim3 grid((w + kTX - 1) / kTX, (h + kTY - 1) / kTY, B);
-  hipLaunchKernelGGL((prob_regress_kernel<T, CB, true>), grid, dim3(256), smem, s, B, D, h, w,
-                     reinterpret_cast<const T*>(feat), wprob, prob_init, nullptr, nullptr, nullptr, nullptr, logits);
-  return hipGetLastError();
+enum class TailForm { mfma_fused, valu_fused, two_pass };
+struct TailRoute {
+  TailForm form;
+  size_t lds;  // dynamic LDS of the conv kernel
+};
+
+// store: ST_BF16 / ST_F32; base: the stage's channels; pack: the stage has the MFMA packing of its storage type (base 8
+// only). The order of precedence:
+//  1. prob_mfma_kernel: with a pack, its [D][256] column within the LDS limit, and DAMVS_PROB_MFMA (read per call)
+//     allowing it: bf16 unless it starts with '0', fp32 only when it starts with '1' (three MFMAs per product measured
+//     slower than the VALU kernel: cfgC B=4 fp32 1.66 against 1.56 ms per step, profiles/r04/prof_steps_f32_r04j.txt)
+//  2. prob_regress_kernel<T, base, false>: its [D - 1][256] column within the LDS limit
+//  3. two passes: prob_regress_kernel<T, base, true> writes the logits to HBM, regress_kernel reads them
+TailRoute tail_route(int store, int base, int D, bool pack) {
+  const char* v = switch_value(SW_PROB_MFMA);
+  const bool mfma_on = !(v && v[0] == '0') && (store == ST_BF16 || (v && v[0] == '1'));
+  if (pack && prob_mfma_smem(store, D) <= kLdsLimit && mfma_on) return {TailForm::mfma_fused, prob_mfma_smem(store, D)};
+  if (prob_regress_smem(base, D - 1) <= kLdsLimit) return {TailForm::valu_fused, prob_regress_smem(base, D - 1)};
+  return {TailForm::two_pass, prob_regress_smem(base, 0)};
 }
 
 template <typename T>
-hipError_t launch_pc(hipStream_t s, int B, int Cb, int D, int h, int w, const void* feat, const float* wprob,
-                     const float* prob_init, float* logits) {
-  if (Cb == 8) return launch_pc_lds<T, 8>(s, B, D, h, w, feat, wprob, prob_init, logits);
-  if (Cb == 16) return launch_pc_lds<T, 16>(s, B, D, h, w, feat, wprob, prob_init, logits);
-  dim3 grid((h * w + 255) / 256, B);
-  const T* f = reinterpret_cast<const T*>(feat);
-  switch (Cb) {
-    case 8: hipLaunchKernelGGL((prob_conv_kernel<T, 8>), grid, dim3(256), 0, s, B, D, h, w, f, wprob, prob_init, logits); break;
-    case 16: hipLaunchKernelGGL((prob_conv_kernel<T, 16>), grid, dim3(256), 0, s, B, D, h, w, f, wprob, prob_init, logits); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+hipError_t launch_mfma_fused(hipStream_t s, size_t lds, const TailArgs& a) {
+  if (!fits_offsets32((long long)a.B * a.D * a.h * a.w * 16 * (sizeof(T) == 4 ? 2 : 1))) return hipErrorInvalidValue;
+  // 16-byte probability stores need w % 4 == 0 (DAMVS_PROB_VEC=0, read per call: one 4-byte store per pixel and plane)
+  const int vec_ok = (a.w & 3) == 0 && switch_on(SW_PROB_VEC);
+  return launch_big_lds(prob_mfma_kernel<T>, tile_grid(a.B, a.h, a.w), dim3(256), lds, s, a.B, a.D, a.h, a.w,
+                        reinterpret_cast<const T*>(a.feat), reinterpret_cast<const uint4*>(a.apack),
+                        sizeof(T) == 4 ? a.pscale : 1.f, a.prob_init, a.hyps, a.depth, a.conf, a.var, a.prob, vec_ok);
+}
+
+hipError_t launch_valu_fused(hipStream_t s, int store, size_t lds, const TailArgs& a) {
+  return for_store_base(store, a.Cb, [&](auto t, auto cb) {
+    using T = decltype(t);
+    constexpr int CB = decltype(cb)::value;
+    if (!fits_offsets32((long long)a.D * a.h * a.w * CB * (long long)sizeof(T))) return hipErrorInvalidValue;
+    return launch_big_lds(prob_regress_kernel<T, CB, false>, tile_grid(a.B, a.h, a.w), dim3(256), lds, s, a.B, a.D, a.h,
+                          a.w, reinterpret_cast<const T*>(a.feat), a.wprob, a.prob_init, a.hyps, a.depth, a.conf, a.var,
+                          a.prob);
+  });
 }
 
 }  // namespace
 
 hipError_t launch_prob_conv(hipStream_t s, int store, int B, int Cb, int D, int h, int w, const void* feat,
                             const float* wprob, const float* prob_init, float* logits) {
-  return store == ST_BF16 ? launch_pc<bf16_t>(s, B, Cb, D, h, w, feat, wprob, prob_init, logits)
-                          : launch_pc<float>(s, B, Cb, D, h, w, feat, wprob, prob_init, logits);
+  return for_store_base(store, Cb, [&](auto t, auto cb) {
+    using T = decltype(t);
+    constexpr int CB = decltype(cb)::value;
+    if (!fits_offsets32((long long)D * h * w * CB * (long long)sizeof(T))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((prob_regress_kernel<T, CB, true>), tile_grid(B, h, w), dim3(256), prob_regress_smem(CB, 0), s, B,
+                       D, h, w, reinterpret_cast<const T*>(feat), wprob, prob_init, nullptr, nullptr, nullptr, nullptr,
+                       logits);
+    return hipGetLastError();
+  });
 }
 
-hipError_t launch_prob_regress(hipStream_t s, int store, int B, int Cb, int D, int h, int w, const void* feat,
-                               const float* wprob, const float* prob_init, const float* hyps, float* depth,
-                               float* conf, float* var, float* prob) {
-  if (Cb == 8)
-    return store == ST_BF16 ? launch_pr_t<bf16_t, 8>(s, B, D, h, w, feat, wprob, prob_init, hyps, depth, conf, var, prob)
-                            : launch_pr_t<float, 8>(s, B, D, h, w, feat, wprob, prob_init, hyps, depth, conf, var, prob);
-  if (Cb == 16)
-    return store == ST_BF16 ? launch_pr_t<bf16_t, 16>(s, B, D, h, w, feat, wprob, prob_init, hyps, depth, conf, var, prob)
-                            : launch_pr_t<float, 16>(s, B, D, h, w, feat, wprob, prob_init, hyps, depth, conf, var, prob);
-  return hipErrorInvalidValue;
+hipError_t launch_regress(hipStream_t s, int B, int D, int h, int w, const float* logits, const float* hyps,
+                          float* depth, float* conf, float* var, float* prob) {
+  int hw = h * w;
+  hipLaunchKernelGGL(regress_kernel, dim3((hw + 255) / 256, B), dim3(256), 0, s, B, D, hw, logits, hyps, depth, conf,
+                     var, prob);
+  return hipGetLastError();
 }
 
-size_t prob_regress_smem_bytes(int store, int Cb, int D) {
-  if (Cb == 8) return store == ST_BF16 ? prob_regress_smem<bf16_t, 8>(D) : prob_regress_smem<float, 8>(D);
-  return store == ST_BF16 ? prob_regress_smem<bf16_t, 16>(D) : prob_regress_smem<float, 16>(D);
+hipError_t launch_tail(hipStream_t s, int store, const TailArgs& a, const char** what) {
+  const TailRoute r = tail_route(store, a.Cb, a.D, a.apack != nullptr);
+  switch (r.form) {
+    case TailForm::mfma_fused:
+      *what = "prob_mfma launch";
+      return store == ST_BF16 ? launch_mfma_fused<bf16_t>(s, r.lds, a) : launch_mfma_fused<float>(s, r.lds, a);
+    case TailForm::valu_fused:
+      *what = "prob_regress launch";
+      return launch_valu_fused(s, store, r.lds, a);
+    case TailForm::two_pass:
+      break;
+  }
+  *what = nullptr;
+  if (!a.logits) return hipErrorInvalidValue;  // nothing launched
+  *what = "prob conv launch";
+  const hipError_t e = launch_prob_conv(s, store, a.B, a.Cb, a.D, a.h, a.w, a.feat, a.wprob, a.prob_init, a.logits);
+  if (e != hipSuccess) return e;
+  *what = "regress launch";
+  return launch_regress(s, a.B, a.D, a.h, a.w, a.logits, a.hyps, a.depth, a.conf, a.var, a.prob);
 }
 
 // The range check at the end of damvs_stage_forward: depth, confidence and variance maps read once (a grid-stride loop
@@ -610,56 +598,11 @@ hipError_t launch_amax(hipStream_t s, const float* x, long long n, unsigned* slo
   return hipGetLastError();
 }
 
-hipError_t launch_regress(hipStream_t s, int B, int D, int h, int w, const float* logits, const float* hyps,
-                          float* depth, float* conf, float* var, float* prob) {
-  int hw = h * w;
-  hipLaunchKernelGGL(regress_kernel, dim3((hw + 255) / 256, B), dim3(256), 0, s, B, D, hw, logits, hyps, depth, conf,
-                     var, prob);
-  return hipGetLastError();
-}
-
 hipError_t launch_finite_check(hipStream_t s, const float* a, const float* b, const float* c, long long n, int* status) {
   const long long nb = (n + 255) / 256;
   hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)(nb < 512 ? (nb > 0 ? nb : 1) : 512)), dim3(256), 0, s, a, b, c,
                      n, status);
   return hipGetLastError();
-}
-
-}  // namespace damvs
-
-namespace damvs {
-
-size_t prob_mfma_smem(int store, int D) {
-  return 2 * (size_t)kPRVox * 16 * (store == ST_BF16 ? 1 : 2) + (size_t)(D > 0 ? D : 0) * 256 * 4;
-}
-
-hipError_t launch_prob_mfma(hipStream_t s, int store, int B, int D, int h, int w, const void* feat, const void* apack,
-                            float pscale, const float* prob_init, const float* hyps, float* depth, float* conf,
-                            float* var, float* prob) {
-  const size_t smem = prob_mfma_smem(store, D);
-  const int PL = store == ST_BF16 ? 1 : 2;
-  if (D < 1 || smem > 160 * 1024) return hipErrorInvalidValue;
-  if ((long long)B * D * h * w * 16 * PL >= (1LL << 31)) return hipErrorInvalidValue;  // 32-bit buffer offsets
-  const dim3 grid((w + kTX - 1) / kTX, (h + kTY - 1) / kTY, B);
-  // 16-byte probability stores need w % 4 == 0 (DAMVS_PROB_VEC=0, read per call: one 4-byte store per pixel and plane)
-  const int vec_ok = (w & 3) == 0 && switch_on(SW_PROB_VEC);
-  if (store == ST_BF16)
-    return launch_big_lds(prob_mfma_kernel<bf16_t>, grid, dim3(256), smem, s, B, D, h, w,
-                          reinterpret_cast<const bf16_t*>(feat), reinterpret_cast<const uint4*>(apack), 1.f, prob_init,
-                          hyps, depth, conf, var, prob, vec_ok);
-  return launch_big_lds(prob_mfma_kernel<float>, grid, dim3(256), smem, s, B, D, h, w,
-                        reinterpret_cast<const float*>(feat), reinterpret_cast<const uint4*>(apack), pscale, prob_init,
-                        hyps, depth, conf, var, prob, vec_ok);
-}
-
-// The stage regression's prob conv on MFMA for this storage type: bf16 by default (DAMVS_PROB_MFMA=0, read per call:
-// the VALU prob_regress_kernel); fp32 (the split-f16 form) only
-// with DAMVS_PROB_MFMA=1 -- three MFMAs per product measured slower than the VALU kernel (cfgC B=4 fp32: 1.66
-// against 1.56 ms per step, profiles/r04/prof_steps_f32_r04j.txt).
-bool prob_mfma_enabled(int store) {
-  const char* v = switch_value(SW_PROB_MFMA);
-  if (v && v[0] == '0') return false;
-  return store == ST_BF16 || (v && v[0] == '1');
 }
 
 }  // namespace damvs

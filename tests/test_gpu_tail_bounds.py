@@ -48,7 +48,7 @@ Routes (regress_tail, restated in route() and asserted by test_route_table):
 
 each at (D, h, w) = (8, 8, 8), (16, 16, 40), (48, 24, 72), (largest fused D, 8, 40) and (first two-pass D, 8, 40: the
 same conv with TWO = true, then regress_kernel), with and without prob_init, fp32 rows on both fixtures; damvs_regress
-alone on lattice logits at (5, 3, 7) and (32, 24, 40).
+alone on lattice logits at (5, 3, 7), (32, 24, 40), (1, 3, 7), (2, 3, 7) and (9, 8, 40).
 
 Hypotheses. ref is oracle.stage_hypotheses on float64 tensors; the bound is a first-order float32 model of
 hyp_refine_kernel per full-resolution point (hyp_reference): the bilinear taps of the previous depth and variance
@@ -66,16 +66,21 @@ Measured on an MI355X (profiles/r09/pytest_gpu_tail_bounds.txt), largest |got - 
 against the float64 reference; no constant of either model was raised and no kernel defect was found. A kernel trace
 per row (profiles/r09/tail_route_kernels.txt) shows each row launching the kernel the table names.
 
-  route                              prob    depth   conf    var
-  prob_mfma<bf16>                    0.340   0.201   0.226   0.021
-  prob_regress<bf16,8,false>         0.340   0.201   0.226   0.021
-  prob_regress<float,8,false>        0.340   0.201   0.302   0.021
-  prob_mfma<float>                   0.340   0.201   0.302   0.021
-  prob_regress<bf16,16,false>        0.263   0.167   0.200   0.017
-  prob_regress<float,16,false>       0.300   0.224   0.236   0.017
-  two-pass bf16 / fp32, base 8       0.102   0.063   0.089   0.005
-  two-pass bf16 / fp32, base 16      0.104   0.062   0.085   0.004
-  regress_kernel alone               0.190   0.118   0.172   0.021
+  route                              prob    depth   conf    var      r10: prob    depth   conf    var
+  prob_mfma<bf16>                    0.340   0.201   0.226   0.021         0.340   0.201   0.226   0.021
+  prob_regress<bf16,8,false>         0.340   0.201   0.226   0.021         0.340   0.201   0.226   0.021
+  prob_regress<float,8,false>        0.340   0.201   0.302   0.021         0.340   0.201   0.302   0.021
+  prob_mfma<float>                   0.340   0.201   0.302   0.021         0.340   0.201   0.302   0.021
+  prob_regress<bf16,16,false>        0.263   0.167   0.200   0.017         0.263   0.167   0.200   0.017
+  prob_regress<float,16,false>       0.300   0.224   0.236   0.017         0.300   0.224   0.235   0.017
+  two-pass bf16 / fp32, base 8       0.102   0.063   0.089   0.005         0.102   0.063   0.088   0.005
+  two-pass bf16 / fp32, base 16      0.104   0.062   0.085   0.004         0.104   0.062   0.085   0.004
+  regress_kernel alone               0.190   0.118   0.172   0.021         0.269   0.221   0.204   0.025
+
+  r10 (profiles/r10/pytest_gpu_tail_bounds.txt): the three kernels on one regression body (regress_column). Every
+  output of every case above is bitwise the r09 build's (profiles/r10/tail_share_gpu.md; the last digits that differ
+  are the rounding of a maximum over lines printed to four places); regress_kernel alone moves with its three added
+  shapes, (9, 8, 40) giving its largest prob, depth and conf ratios and (2, 3, 7) its largest var ratio.
 
   (equal figures across rows are expected: the logits are exact, so the rows differ only where their regression
   code or their cases do)
@@ -353,7 +358,9 @@ ROWS = [Row(id="bf16-8-mfma", bf16=True, base=8, switch=None, kernel="prob_mfma<
         Row(id="bf16-16", bf16=True, base=16, switch=None, kernel="prob_regress<bf16,16,false>", fused=112, two=120),
         Row(id="f32-16", bf16=False, base=16, switch=None, kernel="prob_regress<float,16,false>", fused=112, two=120)]
 BITWISE_SHAPE = (16, 16, 40)
-REGRESS_ONLY = ((5, 3, 7), (32, 24, 40))
+# (1, 3, 7): the window clipped on both sides, only the last plane; (2, 3, 7): the smallest D with two planes;
+# (9, 8, 40): one full group of 8 hypothesis loads plus one (the fused routes only ever see D % 8 == 0)
+REGRESS_ONLY = ((5, 3, 7), (32, 24, 40), (1, 3, 7), (2, 3, 7), (9, 8, 40))
 
 
 def row_shapes(row):

@@ -48,7 +48,7 @@ int main() {
 # The parse of each switch at the parent commit, written out from its getenv site:
 #   off0: `v && v[0] == '0'` turned the default path off (default on)
 #   on1:  `v && v[0] == '1'` turned the alternative on (default off)
-#   raw:  the caller parses the string itself (DAMVS_CONV0_DZ and DAMVS_CONV0_REUSE, now in conv3d_route; prob_mfma_enabled)
+#   raw:  the caller parses the string itself (DAMVS_CONV0_DZ, DAMVS_CONV0_REUSE: conv3d_route; DAMVS_PROB_MFMA: tail_route)
 # and whether the site kept its first answer (a function-local static) or read the environment at every call.
 PARENT = {
     "DAMVS_PLANES4": ("off0", "LIVE"),

@@ -2,8 +2,9 @@
 
   python tools/kres.py k_conv3d [k_conv2d ...] [--grep PATTERN]
 
-Compiles each csrc/<unit>.hip for gfx950 (the library's flags) and prints one line per kernel instance:
-VGPRs, AGPRs, spills, LDS bytes and waves per SIMD, with the demangled name.
+Compiles each csrc/<unit>.hip for gfx950 with the library's flags for that file (damvsnet_amd/build.py CFLAGS and
+FILE_FLAGS) and prints one line per kernel instance: VGPRs, AGPRs, spills, scratch bytes per lane, LDS bytes and waves
+per SIMD, with the demangled name.
 """
 import argparse
 import os
@@ -12,13 +13,16 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "damvsnet_amd", "csrc")
+sys.path.insert(0, REPO)
+from damvsnet_amd import build  # noqa: E402
+
+CSRC = build.CSRC
 
 
 def table(unit, extra=()):
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(REPO, "include"),
-           "-I" + CSRC, "-x", "hip", "-c", os.path.join(CSRC, unit + ".hip"), "-o", os.devnull,
-           "-Rpass-analysis=kernel-resource-usage"] + list(extra)
+    cmd = [build.HIPCC] + build.CFLAGS + build.FILE_FLAGS.get(unit + ".hip", []) + [
+        "-x", "hip", "-c", os.path.join(CSRC, unit + ".hip"), "-o", os.devnull,
+        "-Rpass-analysis=kernel-resource-usage"] + list(extra)
     err = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], None
     for line in err.splitlines():
@@ -46,9 +50,9 @@ def main():
         for r in table(u):
             if a.grep and not re.search(a.grep, r["name"]):
                 continue
-            print("%4d v %4d a  spill %3d  lds %6d  waves %d  %s" % (
-                r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("VGPRs Spill", -1), r.get("LDS Size [bytes/block]", -1),
-                r.get("Occupancy [waves/SIMD]", -1), r["name"][:150]))
+            print("%4d v %4d a  spill %3d  scratch %4d  lds %6d  waves %d  %s" % (
+                r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("VGPRs Spill", -1), r.get("ScratchSize [bytes/lane]", -1),
+                r.get("LDS Size [bytes/block]", -1), r.get("Occupancy [waves/SIMD]", -1), r["name"][:150]))
 
 
 if __name__ == "__main__":
