@@ -1,7 +1,8 @@
 """Build libdamvs.so in-tree with hipcc for gfx950 (no CMake, no JIT cache).
 
 ``python -m damvsnet_amd.build`` or ``damvsnet_amd.build.build()``. Objects are compiled in
-parallel and linked into ``damvsnet_amd/libdamvs.so``. The library carries the sha256 of the sources,
+parallel and linked into ``damvsnet_amd/libdamvs.so`` (and ``libdamvs_fusion.so`` beside it, SIDE_UNITS).
+The library carries the sha256 of the sources,
 headers and compiler flags it was built from (``damvs_build_id()``, passed as -DDAMVS_BUILD_ID); a rebuild
 is skipped only when that stamp (kept beside the library in ``libdamvs.so.build_id``) equals the hash of the
 tree, and ``_capi.load_library`` refuses an in-tree library whose embedded stamp differs from the sources
@@ -22,6 +23,11 @@ REPO = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(REPO, "include")
 LIB = os.path.join(PKG, "libdamvs.so")
+# Units linked into a library of their own that libdamvs.so depends on (found beside it through an $ORIGIN runpath).
+# The static-rule fusion kernel lives there: tests/isa_pins.json pins the kernels of libdamvs.so,
+# tests/isa_pins_fusion.json the kernels of this one.
+SIDE_LIB = os.path.join(PKG, "libdamvs_fusion.so")
+SIDE_UNITS = ("k_fusion_static.hip",)
 STAMP = LIB + ".build_id"
 OBJ = os.path.join(PKG, "build_obj")
 ARCH = os.environ.get("DAMVS_ARCH", "gfx950")
@@ -39,7 +45,7 @@ FILE_FLAGS = {"k_warp.hip": ["-fno-slp-vectorize"]}
 # (k_planes.hip), the hypotheses / GeoFF depth pyramid / camera algebra (k_geometry.hip), the VALU prob conv,
 # regression, range check and magnitude kernels (k_regress.hip) and depth fusion (k_fusion.hip).
 # Both vectorizers are off there: the loop vectorizer, too, emits packed-FP32 ops (grid-stride loops by two).
-for _f in ("k_planes.hip", "k_geometry.hip", "k_regress.hip", "k_fusion.hip"):
+for _f in ("k_planes.hip", "k_geometry.hip", "k_regress.hip", "k_fusion.hip", "k_fusion_static.hip"):
     FILE_FLAGS[_f] = ["-fno-slp-vectorize", "-fno-vectorize"]
 
 
@@ -79,7 +85,7 @@ def stamp() -> str | None:
 
 
 def _stale(want: str) -> bool:
-    return not os.path.exists(LIB) or stamp() != want
+    return not os.path.exists(LIB) or not os.path.exists(SIDE_LIB) or stamp() != want
 
 
 def _compile(src, build_id):
@@ -107,12 +113,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
         for (_, err), s in zip(results, srcs):
             if err.strip():
                 print("[%s]\n%s" % (os.path.basename(s), err), file=sys.stderr)
-    tmp = LIB + ".tmp"
-    cmd = [HIPCC, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp] + objs
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("link failed:\n%s\n%s" % (" ".join(cmd), r.stderr))
-    os.replace(tmp, LIB)
+    side = [o for o in objs if os.path.basename(o)[:-2] in SIDE_UNITS]
+    soname = os.path.basename(SIDE_LIB)
+    for lib, members, extra in ((SIDE_LIB, side, ["-Wl,-soname," + soname]),
+                                (LIB, [o for o in objs if o not in side], [SIDE_LIB, "-Wl,-rpath,$ORIGIN"])):
+        tmp = lib + ".tmp"
+        cmd = [HIPCC, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp] + members + extra
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed:\n%s\n%s" % (" ".join(cmd), r.stderr))
+        os.replace(tmp, lib)
     with open(STAMP, "w") as f:
         f.write(want + "\n")
     if verbose:

@@ -494,7 +494,14 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #ifndef DAMVS_BUILD_ID
 #define DAMVS_BUILD_ID "unstamped"
 #endif
-const char* damvs_build_id(void) { return DAMVS_BUILD_ID; }
+// The stamp of this library when the fusion library loaded beside it (libdamvs_fusion.so) carries the same one; otherwise
+// both, so that a loader comparing the id with the hash of the sources refuses a stale or foreign pair.
+const char* damvs_build_id(void) {
+  static const std::string id = std::strcmp(fusion_static_build_id(), DAMVS_BUILD_ID) == 0
+                                    ? std::string(DAMVS_BUILD_ID)
+                                    : std::string(DAMVS_BUILD_ID) + " (libdamvs_fusion.so: " + fusion_static_build_id() + ")";
+  return id.c_str();
+}
 
 const char* damvs_last_error_string(void) { return g_err.c_str(); }
 
@@ -1249,14 +1256,14 @@ int damvs_conv2d_border_bias(void* stream, int dtype, int B, int H, int W, int c
                    "border_bias launch");
 }
 
-int damvs_fusion_view(void* stream, int H, int W, int nsrc, const float* depth_ref, const float* const* depth_src,
-                      const float* const* conf, const float* conf_thr, const damvs_fusion_cams* cams, double dist_base,
-                      double rel_diff_base, float* depth_avg, unsigned char* mask, float* xyz) {
+// Validation and camera / pointer packing shared by the two fusion entry points (the thresholds are theirs).
+static int fusion_pack(int H, int W, int nsrc, const float* depth_ref, const float* const* depth_src,
+                       const float* const* conf, const float* conf_thr, const damvs_fusion_cams* cams, float* depth_avg,
+                       unsigned char* mask, float* xyz, FusionArgs& a) {
   if (!depth_ref || !depth_src || !cams || !depth_avg || !mask) return fail(DAMVS_E_ARG, "null argument");
   if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return fail(DAMVS_E_SHAPE, "bad shape %d x %d", H, W);
   if (nsrc < 1 || nsrc > kFusionMaxSrc) return fail(DAMVS_E_SHAPE, "nsrc %d not in [1, %d]", nsrc, kFusionMaxSrc);
   if (conf && (!conf[0] || !conf[1] || !conf[2] || !conf_thr)) return fail(DAMVS_E_ARG, "incomplete confidence maps");
-  FusionArgs a;
   std::memset(&a, 0, sizeof(a));
   a.H = H;
   a.W = W;
@@ -1278,14 +1285,37 @@ int damvs_fusion_view(void* stream, int H, int W, int nsrc, const float* depth_r
   std::memcpy(a.kinv_ref, cams->kinv_ref, sizeof(a.kinv_ref));
   std::memcpy(a.k_ref, cams->k_ref, sizeof(a.k_ref));
   std::memcpy(a.einv_ref, cams->einv_ref, sizeof(a.einv_ref));
+  a.depth_avg = depth_avg;
+  a.mask = mask;
+  a.xyz = xyz;
+  return DAMVS_OK;
+}
+
+int damvs_fusion_view(void* stream, int H, int W, int nsrc, const float* depth_ref, const float* const* depth_src,
+                      const float* const* conf, const float* conf_thr, const damvs_fusion_cams* cams, double dist_base,
+                      double rel_diff_base, float* depth_avg, unsigned char* mask, float* xyz) {
+  FusionArgs a;
+  DAMVS_TRY(fusion_pack(H, W, nsrc, depth_ref, depth_src, conf, conf_thr, cams, depth_avg, mask, xyz, a));
   for (int i = 2; i <= 10; ++i) {
     a.dist_thr[i - 2] = i * dist_base;
     a.rel_thr[i - 2] = (float)(i * rel_diff_base);
   }
-  a.depth_avg = depth_avg;
-  a.mask = mask;
-  a.xyz = xyz;
   return hip_check(launch_fusion_view(static_cast<hipStream_t>(stream), a), "fusion_view launch");
+}
+
+int damvs_fusion_view_static(void* stream, int H, int W, int nsrc, const float* depth_ref,
+                             const float* const* depth_src, const float* const* conf, const float* conf_thr,
+                             const damvs_fusion_cams* cams, double dist_thr, double rel_thr, int thres_view,
+                             float* depth_avg, unsigned char* mask, float* xyz) {
+  FusionArgs a;
+  DAMVS_TRY(fusion_pack(H, W, nsrc, depth_ref, depth_src, conf, conf_thr, cams, depth_avg, mask, xyz, a));
+  if (thres_view < 1) return fail(DAMVS_E_ARG, "thres_view %d < 1", thres_view);
+  // the kernel's 32-bit pixel index must not wrap in the last block of 256
+  if ((long long)H * W > (1LL << 31) - 256) return fail(DAMVS_E_SHAPE, "bad shape %d x %d", H, W);
+  a.dist_thr[0] = dist_thr;
+  a.rel_thr[0] = (float)rel_thr;  // numpy compares the float32 relative difference with the constant in float32
+  return hip_check(launch_fusion_view_static(static_cast<hipStream_t>(stream), a, thres_view),
+                   "fusion_view_static launch");
 }
 
 int damvs_conv2d_destroy(damvs_conv2d* L) {

@@ -193,6 +193,11 @@ struct FusionArgs {
   float* xyz;            // world points of final pixels (0 elsewhere), or nullptr
 };
 hipError_t launch_fusion_view(hipStream_t s, const FusionArgs& a);
+// The static rule (filter/pcd.py): dist_thr[0] / rel_thr[0] carry its two fixed thresholds (the other slots are not
+// read), a pixel is geometrically consistent when at least thres_view sources agree.
+hipError_t launch_fusion_view_static(hipStream_t s, const FusionArgs& a, int thres_view);
+// the source stamp (DAMVS_BUILD_ID) of the library that holds the static-rule kernel (k_fusion_static.hip)
+const char* fusion_static_build_id();
 
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per

@@ -1,12 +1,19 @@
-"""Depth-map fusion on the GPU: the reference's dynamic-consistency
-filter (filter/dypcd.py, `dypcd_filter` / `filter_depth`) with the per-pixel reprojection checks in
-one HIP kernel per reference view (damvs_fusion_view, k_fusion.hip).
+"""Depth-map fusion on the GPU: the reference's two runnable filters
+(test_uni.py --filter_method) with the per-pixel reprojection checks in one HIP kernel per reference view
+(k_fusion.hip):
+  method="dypcd"  the dynamic-consistency filter (filter/dypcd.py, `dypcd_filter` / `filter_depth`): masks at
+                  i * dist_base pixels and i * rel_diff_base relative depth, i = 2..10, a pixel kept when i views
+                  agree at some i (damvs_fusion_view);
+  method="pcd"    the static CasMVSNet filter (filter/pcd.py): one mask per source at dist_thr pixels and rel_thr
+                  relative depth (the reference's constants 1 and 0.01), a pixel kept when at least thres_view
+                  sources agree (damvs_fusion_view_static).
+The third method, gipuma, needs an external CUDA binary and is out of scope.
 
 `fuse_view` is the per-view primitive (device tensors in, averaged depth / masks / world points
-out); `filter_depth` mirrors filter/dypcd.py:179-326 over a scene directory written by the test
-path (cams/, images/, depth_est/, confidence/ PFMs; see mvsio.save_stage_outputs) and writes the
+out); `filter_depth` mirrors filter/dypcd.py:179-326 / filter/pcd.py:116-233 over a scene directory written by
+the test path (cams/, images/, depth_est/, confidence/ PFMs; see mvsio.save_stage_outputs) and writes the
 masks and the PLY point cloud. The reference's defaults (test_uni.py:104-109): conf (0.1, 0.15, 0.9),
-dist_base 1/4, rel_diff_base 1/1300.
+dist_base 1/4, rel_diff_base 1/1300, thres_view 5.
 """
 from __future__ import annotations
 
@@ -41,11 +48,17 @@ def fusion_cams(K_ref, E_ref, srcs):
     return c
 
 
+METHODS = ("dypcd", "pcd")
+
+
 def fuse_view(depth_ref, K_ref, E_ref, srcs, confs=None, conf_thr=(0.1, 0.15, 0.9), dist_base=0.25,
-              rel_diff_base=1 / 1300, want_xyz=True):
+              rel_diff_base=1 / 1300, want_xyz=True, method="dypcd", thres_view=5, dist_thr=1.0, rel_thr=0.01):
     """One reference view. depth_ref (H, W) fp32 CUDA tensor; srcs [(depth (H, W) CUDA, K, E)];
     confs: (final, stage-2, stage-1) confidence maps at (H, W) or None.
+    method "dypcd" reads dist_base / rel_diff_base, method "pcd" reads thres_view / dist_thr / rel_thr.
     -> {'depth_avg', 'photo', 'geo', 'final' (bool), 'xyz' (H, W, 3) world points (0 off-mask)}."""
+    if method not in METHODS:
+        raise ValueError("fusion method %r not in %s" % (method, METHODS))
     for t in [depth_ref] + [s[0] for s in srcs] + list(confs or []):
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == depth_ref.shape):
             raise ValueError("fusion maps must be contiguous (H, W) float32 CUDA tensors of one size")
@@ -60,9 +73,12 @@ def fuse_view(depth_ref, K_ref, E_ref, srcs, confs=None, conf_thr=(0.1, 0.15, 0.
     depth_avg = torch.empty(H, W, device=dev, dtype=torch.float32)
     mask = torch.empty(H, W, device=dev, dtype=torch.uint8)
     xyz = torch.empty(H, W, 3, device=dev, dtype=torch.float32) if want_xyz else None
-    check(lib.damvs_fusion_view(_capi.stream_ptr(dev), H, W, n, depth_ref.data_ptr(), dsrc, cptr, thr, ctypes.byref(cams),
-                                dist_base, rel_diff_base, depth_avg.data_ptr(), mask.data_ptr(),
-                                xyz.data_ptr() if xyz is not None else None))
+    head = (_capi.stream_ptr(dev), H, W, n, depth_ref.data_ptr(), dsrc, cptr, thr, ctypes.byref(cams))
+    outs = (depth_avg.data_ptr(), mask.data_ptr(), xyz.data_ptr() if xyz is not None else None)
+    if method == "pcd":
+        check(lib.damvs_fusion_view_static(*head, dist_thr, rel_thr, int(thres_view), *outs))
+    else:
+        check(lib.damvs_fusion_view(*head, dist_base, rel_diff_base, *outs))
     return {"depth_avg": depth_avg, "photo": (mask & 1).bool(), "geo": (mask & 2).bool(), "final": (mask & 4).bool(),
             "xyz": xyz}
 
@@ -73,10 +89,13 @@ def _save_mask(path, m):
 
 
 def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25,
-                 rel_diff_base=1 / 1300, device="cuda"):
-    """filter/dypcd.py:179-326 for one scene: per reference view of pair.txt, load its cams, image,
-    depth and three confidences (and the sources' depths), run the fusion kernel, save the photo /
-    geo / final masks, collect coloured world points; write the PLY. Returns the point count."""
+                 rel_diff_base=1 / 1300, device="cuda", method="dypcd", thres_view=5):
+    """filter/dypcd.py:179-326 (method "dypcd") or filter/pcd.py:116-233 (method "pcd", args.thres_view) for one
+    scene: per reference view of pair.txt, load its cams, image, depth and three confidences (and the sources'
+    depths), run the fusion kernel, save the photo / geo / final masks, collect coloured world points; write the
+    PLY. Returns the point count."""
+    if method not in METHODS:
+        raise ValueError("fusion method %r not in %s" % (method, METHODS))
     pairs = mvsio.read_pair_file(os.path.join(pair_folder, "pair.txt"))
     cam = lambda v: mvsio.read_camera_parameters(os.path.join(scan_folder, "cams", "%08d_cam.txt" % v))
     pfm = lambda kind, v, sfx="": torch.from_numpy(np.ascontiguousarray(
@@ -89,7 +108,8 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0
         confs = (pfm("confidence", ref_view), pfm("confidence", ref_view, "_stage2"),
                  pfm("confidence", ref_view, "_stage1"))
         srcs = [(pfm("depth_est", v),) + cam(v) for v in src_views]
-        r = fuse_view(pfm("depth_est", ref_view), K_ref, E_ref, srcs, confs, conf, dist_base, rel_diff_base)
+        r = fuse_view(pfm("depth_est", ref_view), K_ref, E_ref, srcs, confs, conf, dist_base, rel_diff_base,
+                      method=method, thres_view=thres_view)
         fin = r["final"].cpu().numpy()
         for kind in ("photo", "geo", "final"):
             _save_mask(os.path.join(out_folder, "mask", "%08d_%s.png" % (ref_view, kind)), r[kind].cpu().numpy())

@@ -305,6 +305,19 @@ int damvs_fusion_view(void* stream, int H, int W, int nsrc, const float* depth_r
                       const float* const* conf, const float* conf_thr, const damvs_fusion_cams* cams, double dist_base,
                       double rel_diff_base, float* depth_avg, unsigned char* mask, float* xyz);
 
+/* The same view under the reference's static rule (filter/pcd.py:58-113, 142-170, 190-208, the CasMVSNet filter):
+ * a source agrees when its reprojection error is < dist_thr pixels (float64) and its relative depth difference is
+ * < (float)rel_thr (float32); the reference's constants are dist_thr = 1, rel_thr = 0.01. The geometric mask is
+ * "at least thres_view sources agree" (args.thres_view); the agreeing reprojected depths are averaged with the
+ * reference depth. Unlike dypcd.py, pcd.py divides by the reprojected z unguarded: a zero depth gives inf / NaN and
+ * fails both tests. Maps, conf, conf_thr, cams and the outputs are those of damvs_fusion_view.
+ * 1 <= nsrc <= DAMVS_FUSION_MAX_SRC (DAMVS_E_SHAPE otherwise); thres_view >= 1 (DAMVS_E_ARG otherwise); a thres_view
+ * above nsrc is legal and gives an empty geometric mask, as in the reference. */
+int damvs_fusion_view_static(void* stream, int H, int W, int nsrc, const float* depth_ref,
+                             const float* const* depth_src, const float* const* conf, const float* conf_thr,
+                             const damvs_fusion_cams* cams, double dist_thr, double rel_thr, int thres_view,
+                             float* depth_avg, unsigned char* mask, float* xyz);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@
   python tools/isa.py [--lib PATH] --kernel SUBSTR [--out F] one kernel's instructions (addresses and encodings dropped)
   python tools/isa.py [--lib PATH] --hash SUBSTR             sha256 (16 hex) of each matching kernel's instruction text
   python tools/isa.py [--lib PATH] --mix SUBSTR              instruction-class counts of each matching kernel
-  python tools/isa.py --update-pins --validated-by LOG       rewrite tests/isa_pins.json from the built library
+  python tools/isa.py [--lib PATH --pins FILE] --update-pins --validated-by LOG
+                                                            rewrite tests/isa_pins.json (or FILE) from the built library
                                                             (only after the GPU stream tests passed on this build:
                                                             LOG is the committed pytest log that shows it)
 
@@ -114,17 +115,18 @@ def main():
     g.add_argument("--mix")
     g.add_argument("--update-pins", action="store_true")
     ap.add_argument("--validated-by", default=None)
+    ap.add_argument("--pins", default=PINS, help="pin file to rewrite (libdamvs_fusion.so: tests/isa_pins_fusion.json)")
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.update_pins:
         import json
         if not a.validated_by or not os.path.exists(os.path.join(REPO, a.validated_by)):
             sys.exit("--validated-by must name the committed GPU pytest log of tests/test_gpu_streams.py on this build")
-        with open(PINS, "w") as f:
+        with open(a.pins, "w") as f:
             json.dump({"compiler": compiler(), "validated_by": a.validated_by, "kernels": hashes(a.lib)}, f, indent=1,
                       sort_keys=True)
             f.write("\n")
-        print("wrote", PINS)
+        print("wrote", a.pins)
         return
     ks = disassemble(a.lib)
     names = sorted(ks)
