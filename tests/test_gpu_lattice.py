@@ -81,6 +81,11 @@ def check_fixture(what, ref, pre, bound, unit, relu):
     assert float(bound.max()) / unit < 2 ** 24, (what, float(bound.max()), unit)
     assert torch.equal((ref / unit).round() * unit, ref), (what, "off the lattice")
     assert torch.equal(ref.to(BF16).double(), ref), (what, "not bf16-storable", float(ref.abs().max()))
+    check_occupancy(what, ref, pre, relu)
+
+
+def check_occupancy(what, ref, pre, relu):
+    """Condition 3 of check_fixture."""
     nz = float((ref != 0).double().mean())
     assert nz >= 0.25, (what, "non-zero fraction", nz)
     if relu:
@@ -128,19 +133,25 @@ def _conv2d_weight_density(fan):
 
 @functools.lru_cache(maxsize=2)
 def conv2d_fixture(i):
+    return conv2d_build(i)
+
+
+def conv2d_build(i, tweak=None, seed=None, act_density=0.5):
     """Lattice weights, bias, tensor inputs, planar inputs, res_pre and res_post of row i of test_gpu_frontend.CASES,
-    with the float64 reference on the explicitly concatenated input."""
+    with the float64 reference on the explicitly concatenated input. tweak(w, full, transposed) -> (w, full) replaces
+    the weights and the concatenated input before the reference is taken (test_gpu_split.py); seed / act_density override
+    the generator's seed and the density of the tensor and planar inputs."""
     case = CONV2D_CASES[i]
     tr, k, s, p, op, c0, c1, geo, cout, relu, pre, post_up = case[:12]
     H, W = case[12] if len(case) > 12 else (20, 24)
-    g = torch.Generator().manual_seed(1000 + i)
+    g = torch.Generator().manual_seed(1000 + i if seed is None else seed)
     cin = c0 + c1 + len(geo)
     fan = cin * k * k // (s * s if tr else 1)
     w = lattice((cin, cout, k, k) if tr else (cout, cin, k, k), WGT, _conv2d_weight_density(fan), g)
     bias = lattice((cout,), WGT, 1.0, g)
-    a = lattice((B, c0, H, W), ACT, 0.5, g) if c0 else None
-    b = lattice((B, c1, H, W), ACT, 0.5, g) if c1 else None
-    gp = lattice((B, len(geo), H, W), ACT, 0.5, g) if geo else None
+    a = lattice((B, c0, H, W), ACT, act_density, g) if c0 else None
+    b = lattice((B, c1, H, W), ACT, act_density, g) if c1 else None
+    gp = lattice((B, len(geo), H, W), ACT, act_density, g) if geo else None
     full = torch.zeros(B, cin, H, W, dtype=torch.float64)  # the reference input in weight-channel order
     tensor_at = [c for c in range(cin) if c not in geo]
     if c0:
@@ -149,6 +160,11 @@ def conv2d_fixture(i):
         full[:, tensor_at[c0:]] = b
     for j, gc in enumerate(geo):
         full[:, gc] = gp[:, j]
+    if tweak is not None:
+        w, full = tweak(w, full, tr)
+        a = full[:, tensor_at[:c0]] if c0 else None
+        b = full[:, tensor_at[c0:]] if c1 else None
+        gp = full[:, list(geo)] if geo else None
     if tr:
         conv = lambda x, w_: F.conv_transpose2d(x, w_, None, stride=s, padding=p, output_padding=op)  # noqa: E731
     else:
@@ -162,7 +178,7 @@ def conv2d_fixture(i):
                             post.abs() if post_up else None, post_up)[0]
     return types.SimpleNamespace(case=case, H=H, W=W, cin=cin, tensor_at=tensor_at, w=w, bias=bias, a=a, b=b, gp=gp,
                                  full=full, conv=conv, acc=acc, res_pre=res_pre, post=post, ref=ref, preact=preact,
-                                 bound=bound, unit=0.5)
+                                 bound=bound, unit=0.5, tr=tr, relu=relu)
 
 
 # ---------------------------------------------------------------------------------------------- fused FPN top
@@ -173,14 +189,21 @@ _FPN_S = ((2,), (1, 2), (0, 1), (0,))  # 3x3 taps merged into each transposed k4
 
 @functools.lru_cache(maxsize=2)
 def fpn_fixture(Bn, H, W):
+    return fpn_build(Bn, H, W)
+
+
+def fpn_build(Bn, H, W, tweak=None):
     """Lattice inner2 (1x1, 8 -> 32, bias) / out3 (3x3, 32 -> 8) and inputs; the unfused float64 reference
-    out3(up2(f) + inner2(c0)); and the re-associated weights (frontend_hip.fpn_top_layers) restated in float64."""
+    out3(up2(f) + inner2(c0)); and the re-associated weights (frontend_hip.fpn_top_layers) restated in float64.
+    tweak(c0, f) -> (c0, f) replaces the two inputs before the reference is taken (test_gpu_split.py)."""
     g = torch.Generator().manual_seed(H * W)
     W1 = lattice((32, 8), WGT, 0.25, g)
     b1 = lattice((32,), WGT, 1.0, g)
     W3 = lattice((8, 32, 3, 3), WGT, 0.125, g)
     c0 = lattice((Bn, 8, H, W), ACT, 0.5, g)
     f = lattice((Bn, 32, H // 2, W // 2), ACT, 0.5, g)
+    if tweak is not None:
+        c0, f = tweak(c0, f)
     inner = lambda x, w_, b_: F.conv2d(x, w_[:, :, None, None], b_)  # noqa: E731
     ref = F.conv2d(upsample(f, 2) + inner(c0, W1, b1), W3, padding=1)
     bound = F.conv2d(upsample(f.abs(), 2) + inner(c0.abs(), W1.abs(), b1.abs()), W3.abs(), padding=1)
@@ -217,12 +240,13 @@ def fold_bn_numpy(weight, bias, mean, var, eps):
 
 
 @functools.lru_cache(maxsize=None)
-def unet_net(C):
+def unet_net(C, zero_shift=False):
     """CostRegNet(C, 8) with lattice conv weights and BatchNorms that fold to exact lattice values: per-channel scale in
     {0.5, 1, 2} (from every (weight, variance) pair of BN_COMBOS), running_mean 0, and a half-integer bias =
     scale * b with b in {+-0.5, +-1} (+-1, +-2 where the scale is 0.5): a channel is then a power-of-two multiple of
-    the lattice tensor conv + b, and whether it is storable does not depend on its scale. Returns (net, {layer name:
-    (intended scale, intended shift)})."""
+    the lattice tensor conv + b, and whether it is storable does not depend on its scale. zero_shift: the same net
+    (same draws) with every BatchNorm bias 0, so that each layer is homogeneous in its input. Returns (net, {layer
+    name: (intended scale, intended shift)})."""
     from damvsnet_amd.layers import CostRegNet
     g = torch.Generator().manual_seed(77 + C)
     net = CostRegNet(C, 8)
@@ -239,6 +263,8 @@ def unet_net(C):
             scale = bw / vb.sqrt()
             half = lattice((co,), WGT, 1.0, g).float()
             shift = scale * torch.where(scale == 0.5, 2 * half, half)  # a half-integer in {+-0.5, +-1, +-2}
+            if zero_shift:
+                shift = torch.zeros_like(shift)
             assert m.bn.eps == BN_EPS
             m.bn.weight.copy_(bw)
             m.bn.bias.copy_(shift)
@@ -251,14 +277,21 @@ def unet_net(C):
 
 @functools.lru_cache(maxsize=3)
 def unet_fixture(C, shape, layer):
-    """Layer `layer` (0..9) of unet_net(C) on its own lattice input of its level's shape, a lattice skip tensor for the
-    deconvs, and the float64 reference relu(conv * scale + shift) (+ skip)."""
+    return unet_build(unet_net(C), C, shape, layer)
+
+
+def unet_build(net_want, C, shape, layer, tweak=None):
+    """Layer `layer` (0..9) of the net (unet_net's return value) on its own lattice input of its level's shape, a
+    lattice skip tensor for the deconvs, and the float64 reference relu(conv * scale + shift) (+ skip). tweak(x) -> x
+    replaces the input before the reference is taken (test_gpu_split.py)."""
     from damvsnet_amd.costmodel import unet_layers
     name, cin, cout, li, lo, tr, skip = unet_layers(C, 8)[layer]
     D, h, w = shape
-    net, want = unet_net(C)
+    net, want = net_want
     g = torch.Generator().manual_seed(C * 1000 + layer * 10 + UNET_SHAPES.index(shape))
     x = lattice((B, cin, D >> li, h >> li, w >> li), ACT, 0.5, g)
+    if tweak is not None:
+        x = tweak(x)
     wgt = getattr(net, name).conv.weight.detach().double()
     scale, shift = want[name]
     if tr:
@@ -270,7 +303,8 @@ def unet_fixture(C, shape, layer):
     sk = lattice(acc.shape, ACT, 0.5, g) if skip else None
     ref, preact = layer_reference(acc, scale, shift, None, True, sk)
     bound = layer_reference(conv(x.abs(), wgt.abs()), scale, shift.abs(), None, False, sk.abs() if skip else None)[0]
-    return types.SimpleNamespace(name=name, x=x, skip=sk, ref=ref, preact=preact, bound=bound, unit=0.25)
+    return types.SimpleNamespace(name=name, x=x, skip=sk, ref=ref, preact=preact, bound=bound, unit=0.25, w=wgt,
+                                 scale=scale.double(), shift=shift.double(), conv=conv, acc=acc, tr=bool(tr))
 
 
 # ---------------------------------------------------------------------------------------------- the CPU tests
@@ -349,8 +383,12 @@ DT_IDS = {BF16: "bf16", F32: "f32"}
 def test_conv2d_layer_exact(i, dtype, _lib):
     """Every form of test_gpu_frontend.CASES on lattice data: equal to the float64 reference on the first cout channels,
     exactly 0 on the padded channels up to cout_store."""
+    run_conv2d_layer(conv2d_fixture(i), dtype, "conv2d case %d %s" % (i, DT_IDS[dtype]))
+
+
+def run_conv2d_layer(fx, dtype, what, equal=assert_lattice_equal):
+    """The body of test_conv2d_layer_exact on fixture fx (test_gpu_split.py runs it on its own fixtures)."""
     from damvsnet_amd.frontend_hip import HipConv2d, planes
-    fx = conv2d_fixture(i)
     tr, k, s, p, op, c0, c1, geo, cout, relu, pre, post_up = fx.case[:12]
     H, W = fx.H, fx.W
     conv = (nn.ConvTranspose2d(fx.cin, cout, k, stride=s, padding=p, output_padding=op) if tr
@@ -373,8 +411,7 @@ def test_conv2d_layer_exact(i, dtype, _lib):
             res_post=dev(padc(fx.post)) if post_up else None, post_up=max(post_up, 1))
     got = out.cpu()
     assert got.shape == (B,) + tuple(fx.ref.shape[2:]) + (cs,)
-    assert_lattice_equal(got[..., :cout].contiguous(), channels_last(fx.ref).to(dtype),
-                         "conv2d case %d %s" % (i, DT_IDS[dtype]))
+    equal(got[..., :cout].contiguous(), channels_last(fx.ref).to(dtype), what)
     assert not bool(got[..., cout:].any()), "padded channels %d..%d are not zero" % (cout, cs)
 
 
@@ -386,10 +423,14 @@ def test_fpn_top_fused_exact(Bn, H, W, dt, _lib):
     the unfused out3(up2(f) + inner2(c0)) in float64: equal at every pixel, the border ring and corners included. The
     composed weights are multiples of 0.25 below 64, so they are exact bf16 values, and scaled by a power of two they
     are exact f16 values with a zero lo half (asserted on the CPU from the packed values): both dtypes are exact."""
+    run_fpn_top(fpn_fixture(Bn, H, W), Bn, H, W, dt)
+
+
+def run_fpn_top(fx, Bn, H, W, dt, equal=assert_lattice_equal):
+    """The body of test_fpn_top_fused_exact on fixture fx (test_gpu_split.py runs it on its own fixtures)."""
     from damvsnet_amd import _capi
     from damvsnet_amd.engine import DTYPES
     from damvsnet_amd.frontend_hip import fpn_top_layers, pack_fpn_top, pack_fpn_top_split
-    fx = fpn_fixture(Bn, H, W)
     inner2, out3 = nn.Conv2d(8, 32, 1, bias=True), nn.Conv2d(32, 8, 3, padding=1, bias=False)
     with torch.no_grad():
         inner2.weight.copy_(fx.W1[:, :, None, None])
@@ -413,13 +454,13 @@ def test_fpn_top_fused_exact(Bn, H, W, dt, _lib):
                                                   ap.data_ptr(), ws, bd.data_ptr(), o.data_ptr()))
     o2 = conv(Bn, H, W, c0d, res_pre=up(Bn, H // 2, W // 2, fd))
     want_prefix = channels_last(fx.prefix).to(dt)
-    assert_lattice_equal(o.cpu(), want_prefix, "fpn top fused %s, before the border fix-up" % DT_IDS[dt])
+    equal(o.cpu(), want_prefix, "fpn top fused %s, before the border fix-up" % DT_IDS[dt])
     for t in (o, o2):
         _capi.check(lib.damvs_conv2d_border_bias(_capi.stream_ptr(t.device), DTYPES[dt], Bn, H, W, 8, 8,
                                                  _capi.float_ptr(corr), t.data_ptr()))
     want = channels_last(fx.ref).to(dt)
-    assert_lattice_equal(o.cpu(), want, "fpn top fused %s" % DT_IDS[dt])
-    assert_lattice_equal(o2.cpu(), want, "fpn top in two launches %s" % DT_IDS[dt])
+    equal(o.cpu(), want, "fpn top fused %s" % DT_IDS[dt])
+    equal(o2.cpu(), want, "fpn top in two launches %s" % DT_IDS[dt])
 
 
 _ENGINES = {}
@@ -451,20 +492,26 @@ def test_unet_layer_exact(C, shape, layer, mode, switch, _lib, monkeypatch):
     without an output slot); the recorded output maximum equals max |ref| of each batch element exactly, read over
     every replica word of the slot. With DAMVS_CONV_NO_ZSLIDE / DAMVS_DECONV_NO_ZSLIDE the tile and gather kernels
     that other shapes fall back to meet the reference themselves, not only their z-streamed siblings."""
-    from damvsnet_amd.sharded import _SLOTS
     dtype = BF16 if mode == "bf16" else F32
     fx = unet_fixture(C, shape, layer)
-    eng = _engine(C, dtype)
     if switch:
         monkeypatch.setenv(switch, "1")
+    run_unet_layer(_engine(C, dtype), fx.x, fx.skip, fx.ref, layer, shape, mode,
+                   "C %d %s %s %s %s" % (C, shape, fx.name, mode, switch or ""))
+
+
+def run_unet_layer(eng, x64, skip64, ref64, layer, shape, mode, what, equal=assert_lattice_equal):
+    """The body of test_unet_layer_exact: layer `layer` of engine eng on the float64 input x64 (and skip64 for the
+    deconvs) against ref64 (test_gpu_split.py runs it on its own fixtures)."""
+    from damvsnet_amd.sharded import _SLOTS
+    dtype = BF16 if mode == "bf16" else F32
     D, h, w = shape
-    x = channels_last(fx.x).to(DEV, dtype)
-    want = channels_last(fx.ref).to(dtype)
-    if fx.skip is not None:
-        out = channels_last(fx.skip).to(DEV, dtype)
+    x = channels_last(x64).to(DEV, dtype)
+    want = channels_last(ref64).to(dtype)
+    if skip64 is not None:
+        out = channels_last(skip64).to(DEV, dtype)
     else:  # a conv must overwrite whatever its output held
         out = torch.full(want.shape, 3.0, device=DEV, dtype=dtype)
-    what = "C %d %s %s %s %s" % (C, shape, fx.name, mode, switch or "")
     if mode != "f32-slots":
         eng.unet_layer(layer, D, h, w, x, out)
     else:
@@ -475,8 +522,8 @@ def test_unet_layer_exact(C, shape, layer, mode, switch, _lib, monkeypatch):
         torch.cuda.synchronize()
         if sout is not None:
             rec = slots[sout].cpu().amax(1).view(torch.float32)  # non-negative floats order as their bit patterns
-            exp = fx.ref.abs().reshape(B, -1).amax(1).float()
+            exp = ref64.abs().reshape(B, -1).amax(1).float()
             assert torch.equal(rec, exp), (what, "recorded max", rec.tolist(), "max |ref|", exp.tolist())
             untouched = [t for t in range(slots.shape[0]) if t not in (sin, sout)]
             assert not bool(slots[untouched].any()), (what, "another tensor's slot was written")
-    assert_lattice_equal(out.cpu(), want, what)
+    equal(out.cpu(), want, what)
