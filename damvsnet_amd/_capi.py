@@ -115,6 +115,9 @@ SIGNATURES = (
                                          ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_float),
                                          ctypes.POINTER(DamvsFusionCams), ctypes.c_double, ctypes.c_double, c_int,
                                          c_void_p, c_void_p, c_void_p)),
+    ("damvs_fusion_cloud_scratch", c_int, (c_int, c_int)),
+    ("damvs_fusion_cloud", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
+                                   c_void_p, ctypes.c_longlong, c_void_p)),
     ("damvs_conv2d_border_bias", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                          ctypes.POINTER(ctypes.c_float), c_void_p)),
 )

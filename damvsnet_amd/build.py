@@ -1,8 +1,8 @@
 """Build libdamvs.so in-tree with hipcc for gfx950 (no CMake, no JIT cache).
 
 ``python -m damvsnet_amd.build`` or ``damvsnet_amd.build.build()``. Objects are compiled in
-parallel and linked into ``damvsnet_amd/libdamvs.so`` (and ``libdamvs_fusion.so`` beside it, SIDE_UNITS).
-The library carries the sha256 of the sources,
+parallel and linked into ``damvsnet_amd/libdamvs.so`` (and ``libdamvs_fusion.so``, ``libdamvs_cloud.so`` beside it,
+SIDE_LIBS). The library carries the sha256 of the sources,
 headers and compiler flags it was built from (``damvs_build_id()``, passed as -DDAMVS_BUILD_ID); a rebuild
 is skipped only when that stamp (kept beside the library in ``libdamvs.so.build_id``) equals the hash of the
 tree, and ``_capi.load_library`` refuses an in-tree library whose embedded stamp differs from the sources
@@ -28,6 +28,11 @@ LIB = os.path.join(PKG, "libdamvs.so")
 # tests/isa_pins_fusion.json the kernels of this one.
 SIDE_LIB = os.path.join(PKG, "libdamvs_fusion.so")
 SIDE_UNITS = ("k_fusion_static.hip",)
+# The point-cloud compaction kernels (count, scan, scatter), pinned by tests/isa_pins_cloud.json.
+CLOUD_LIB = os.path.join(PKG, "libdamvs_cloud.so")
+CLOUD_UNITS = ("k_cloud.hip",)
+# every side library with its units, in link order (all before libdamvs.so)
+SIDE_LIBS = ((SIDE_LIB, SIDE_UNITS), (CLOUD_LIB, CLOUD_UNITS))
 STAMP = LIB + ".build_id"
 OBJ = os.path.join(PKG, "build_obj")
 ARCH = os.environ.get("DAMVS_ARCH", "gfx950")
@@ -45,7 +50,7 @@ FILE_FLAGS = {"k_warp.hip": ["-fno-slp-vectorize"]}
 # (k_planes.hip), the hypotheses / GeoFF depth pyramid / camera algebra (k_geometry.hip), the VALU prob conv,
 # regression, range check and magnitude kernels (k_regress.hip) and depth fusion (k_fusion.hip).
 # Both vectorizers are off there: the loop vectorizer, too, emits packed-FP32 ops (grid-stride loops by two).
-for _f in ("k_planes.hip", "k_geometry.hip", "k_regress.hip", "k_fusion.hip", "k_fusion_static.hip"):
+for _f in ("k_planes.hip", "k_geometry.hip", "k_regress.hip", "k_fusion.hip", "k_fusion_static.hip", "k_cloud.hip"):
     FILE_FLAGS[_f] = ["-fno-slp-vectorize", "-fno-vectorize"]
 
 
@@ -85,7 +90,7 @@ def stamp() -> str | None:
 
 
 def _stale(want: str) -> bool:
-    return not os.path.exists(LIB) or not os.path.exists(SIDE_LIB) or stamp() != want
+    return not all(os.path.exists(p) for p in (LIB,) + tuple(lib for lib, _ in SIDE_LIBS)) or stamp() != want
 
 
 def _compile(src, build_id):
@@ -113,10 +118,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
         for (_, err), s in zip(results, srcs):
             if err.strip():
                 print("[%s]\n%s" % (os.path.basename(s), err), file=sys.stderr)
-    side = [o for o in objs if os.path.basename(o)[:-2] in SIDE_UNITS]
-    soname = os.path.basename(SIDE_LIB)
-    for lib, members, extra in ((SIDE_LIB, side, ["-Wl,-soname," + soname]),
-                                (LIB, [o for o in objs if o not in side], [SIDE_LIB, "-Wl,-rpath,$ORIGIN"])):
+    unit = lambda o: os.path.basename(o)[:-2]
+    side_units = [u for _, units in SIDE_LIBS for u in units]
+    # libdamvs.so finds the side libraries beside itself ($ORIGIN); the package directory it was built in follows, so
+    # that a copy of libdamvs.so placed beside a replacement of one of them (tests/test_fusion_static.py
+    # test_foreign_fusion_library_is_refused) still loads the others from here
+    links = [(lib, [o for o in objs if unit(o) in units], ["-Wl,-soname," + os.path.basename(lib)])
+             for lib, units in SIDE_LIBS]
+    links.append((LIB, [o for o in objs if unit(o) not in side_units],
+                  [lib for lib, _ in SIDE_LIBS] + ["-Wl,-rpath,$ORIGIN:" + PKG]))
+    for lib, members, extra in links:
         tmp = lib + ".tmp"
         cmd = [HIPCC, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp] + members + extra
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -494,12 +494,17 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #ifndef DAMVS_BUILD_ID
 #define DAMVS_BUILD_ID "unstamped"
 #endif
-// The stamp of this library when the fusion library loaded beside it (libdamvs_fusion.so) carries the same one; otherwise
-// both, so that a loader comparing the id with the hash of the sources refuses a stale or foreign pair.
+// The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so) carry the same
+// one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
-  static const std::string id = std::strcmp(fusion_static_build_id(), DAMVS_BUILD_ID) == 0
-                                    ? std::string(DAMVS_BUILD_ID)
-                                    : std::string(DAMVS_BUILD_ID) + " (libdamvs_fusion.so: " + fusion_static_build_id() + ")";
+  static const std::string id = [] {
+    std::string s(DAMVS_BUILD_ID);
+    const std::pair<const char*, const char*> side[] = {{"libdamvs_fusion.so", fusion_static_build_id()},
+                                                        {"libdamvs_cloud.so", fusion_cloud_build_id()}};
+    for (const auto& l : side)
+      if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
+    return s;
+  }();
   return id.c_str();
 }
 
@@ -1316,6 +1321,33 @@ int damvs_fusion_view_static(void* stream, int H, int W, int nsrc, const float* 
   a.rel_thr[0] = (float)rel_thr;  // numpy compares the float32 relative difference with the constant in float32
   return hip_check(launch_fusion_view_static(static_cast<hipStream_t>(stream), a, thres_view),
                    "fusion_view_static launch");
+}
+
+int damvs_fusion_cloud_scratch(int H, int W) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return fail(DAMVS_E_SHAPE, "bad shape %d x %d", H, W);
+  return fusion_cloud_tiles((long long)H * W) + 2;
+}
+
+int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, const float* xyz, const unsigned char* rgb,
+                       unsigned int* scratch, long long scratch_elems, unsigned char* records, long long capacity,
+                       unsigned long long* cursor) {
+  // records may be null when nothing can be written to it (capacity 0: the call only counts)
+  if (!mask || !xyz || !rgb || !scratch || !cursor || (!records && capacity != 0)) return fail(DAMVS_E_ARG, "null argument");
+  const int need = damvs_fusion_cloud_scratch(H, W);
+  if (need < 0) return need;
+  if (scratch_elems < need) return fail(DAMVS_E_ARG, "scratch of %lld elements, %d x %d needs %d", scratch_elems, H, W, need);
+  if (capacity < 0) return fail(DAMVS_E_ARG, "capacity %lld < 0", capacity);
+  CloudArgs a;
+  a.n = (long long)H * W;
+  a.ntiles = (unsigned)(need - 2);
+  a.mask = mask;
+  a.xyz = xyz;
+  a.rgb = rgb;
+  a.scratch = scratch;
+  a.records = records;
+  a.capacity = capacity;
+  a.cursor = cursor;
+  return hip_check(launch_fusion_cloud(static_cast<hipStream_t>(stream), a), "fusion_cloud launch");
 }
 
 int damvs_conv2d_destroy(damvs_conv2d* L) {

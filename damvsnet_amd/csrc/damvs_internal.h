@@ -199,6 +199,24 @@ hipError_t launch_fusion_view_static(hipStream_t s, const FusionArgs& a, int thr
 // the source stamp (DAMVS_BUILD_ID) of the library that holds the static-rule kernel (k_fusion_static.hip)
 const char* fusion_static_build_id();
 
+// ---------------------------------------------------------------- fused point cloud (k_cloud.hip, libdamvs_cloud.so)
+constexpr int kCloudTile = 256;  // consecutive pixels per block of the count and scatter launches
+struct CloudArgs {
+  long long n;                // H * W
+  unsigned ntiles;            // fusion_cloud_tiles(n)
+  const unsigned char* mask;  // [n] as the fusion kernels write it; bit value 4 (final) selects
+  const float* xyz;           // [n][3]
+  const unsigned char* rgb;   // [n][3]
+  unsigned* scratch;          // [ntiles + 2]: tile counts / offsets, then the cursor before the call (low, high)
+  unsigned char* records;     // 15-byte records
+  long long capacity;         // records that fit; the ones past it are counted, not written
+  unsigned long long* cursor; // records written so far by the calls on this stream
+};
+int fusion_cloud_tiles(long long n);
+// count, scan, scatter on s; calls that share a cursor must be on one stream
+hipError_t launch_fusion_cloud(hipStream_t s, const CloudArgs& a);
+const char* fusion_cloud_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -14,6 +14,10 @@ out); `filter_depth` mirrors filter/dypcd.py:179-326 / filter/pcd.py:116-233 ove
 the test path (cams/, images/, depth_est/, confidence/ PFMs; see mvsio.save_stage_outputs) and writes the
 masks and the PLY point cloud. The reference's defaults (test_uni.py:104-109): conf (0.1, 0.15, 0.9),
 dist_base 1/4, rel_diff_base 1/1300, thres_view 5.
+
+`fuse_scene` is filter_depth with the scene kept on the device: every map uploaded once, and the coloured points of
+each view appended in pixel order to one device buffer by `compact_cloud` (k_cloud.hip, damvs_fusion_cloud), so that
+one copy of count * 15 bytes is the PLY's body. Same files in, same files out.
 """
 from __future__ import annotations
 
@@ -51,12 +55,9 @@ def fusion_cams(K_ref, E_ref, srcs):
 METHODS = ("dypcd", "pcd")
 
 
-def fuse_view(depth_ref, K_ref, E_ref, srcs, confs=None, conf_thr=(0.1, 0.15, 0.9), dist_base=0.25,
-              rel_diff_base=1 / 1300, want_xyz=True, method="dypcd", thres_view=5, dist_thr=1.0, rel_thr=0.01):
-    """One reference view. depth_ref (H, W) fp32 CUDA tensor; srcs [(depth (H, W) CUDA, K, E)];
-    confs: (final, stage-2, stage-1) confidence maps at (H, W) or None.
-    method "dypcd" reads dist_base / rel_diff_base, method "pcd" reads thres_view / dist_thr / rel_thr.
-    -> {'depth_avg', 'photo', 'geo', 'final' (bool), 'xyz' (H, W, 3) world points (0 off-mask)}."""
+def _fuse_view_raw(depth_ref, K_ref, E_ref, srcs, confs, conf_thr, dist_base, rel_diff_base, want_xyz, method,
+                   thres_view, dist_thr, rel_thr):
+    """fuse_view's launch -> (depth_avg, mask uint8 (bit 0 photo, bit 1 geometric, bit 2 final), xyz or None)."""
     if method not in METHODS:
         raise ValueError("fusion method %r not in %s" % (method, METHODS))
     for t in [depth_ref] + [s[0] for s in srcs] + list(confs or []):
@@ -79,8 +80,57 @@ def fuse_view(depth_ref, K_ref, E_ref, srcs, confs=None, conf_thr=(0.1, 0.15, 0.
         check(lib.damvs_fusion_view_static(*head, dist_thr, rel_thr, int(thres_view), *outs))
     else:
         check(lib.damvs_fusion_view(*head, dist_base, rel_diff_base, *outs))
+    return depth_avg, mask, xyz
+
+
+def fuse_view(depth_ref, K_ref, E_ref, srcs, confs=None, conf_thr=(0.1, 0.15, 0.9), dist_base=0.25,
+              rel_diff_base=1 / 1300, want_xyz=True, method="dypcd", thres_view=5, dist_thr=1.0, rel_thr=0.01):
+    """One reference view. depth_ref (H, W) fp32 CUDA tensor; srcs [(depth (H, W) CUDA, K, E)];
+    confs: (final, stage-2, stage-1) confidence maps at (H, W) or None.
+    method "dypcd" reads dist_base / rel_diff_base, method "pcd" reads thres_view / dist_thr / rel_thr.
+    -> {'depth_avg', 'photo', 'geo', 'final' (bool), 'xyz' (H, W, 3) world points (0 off-mask)}."""
+    depth_avg, mask, xyz = _fuse_view_raw(depth_ref, K_ref, E_ref, srcs, confs, conf_thr, dist_base, rel_diff_base,
+                                          want_xyz, method, thres_view, dist_thr, rel_thr)
     return {"depth_avg": depth_avg, "photo": (mask & 1).bool(), "geo": (mask & 2).bool(), "final": (mask & 4).bool(),
             "xyz": xyz}
+
+
+RECORD_BYTES = mvsio.PLY_RECORD_BYTES
+
+
+def compact_cloud(mask, xyz, rgb, records, cursor, scratch=None):
+    """The coloured points of one fused view, appended in row-major pixel order to a record buffer on the device
+    (damvs_fusion_cloud, k_cloud.hip). mask (H, W) uint8 as the fusion kernels write it (bit value 4 selects), xyz
+    (H, W, 3) float32, rgb (H, W, 3) uint8; records: 1-D uint8 CUDA tensor of capacity len // 15 records (x, y, z
+    float32, red, green, blue: mvsio.write_ply's element); cursor: 1-element int64 CUDA tensor, the number of records
+    so far. Record i of the view goes to records[(cursor + i) * 15:] when cursor + i < capacity; cursor advances by
+    the view's count either way (a cursor above the capacity tells how many were needed). Nothing is synchronised;
+    calls that share a cursor must run on one stream. scratch: int32 CUDA tensor of at least
+    damvs_fusion_cloud_scratch(H, W) elements to reuse, or None to allocate. -> the scratch tensor."""
+    H, W = mask.shape if mask.dim() == 2 else (0, 0)
+    dev = mask.device
+    ok = lambda t, dt, shape: t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and \
+        (shape is None or tuple(t.shape) == shape)
+    if not (ok(mask, torch.uint8, (H, W)) and ok(xyz, torch.float32, (H, W, 3)) and ok(rgb, torch.uint8, (H, W, 3))):
+        raise ValueError("compact_cloud takes contiguous CUDA tensors of one device: mask (H, W) uint8, xyz (H, W, 3) "
+                         "float32, rgb (H, W, 3) uint8")
+    if not (ok(records, torch.uint8, None) and records.dim() == 1):
+        raise ValueError("records must be a contiguous 1-D uint8 CUDA tensor")
+    if not (ok(cursor, torch.int64, None) and cursor.numel() == 1):
+        raise ValueError("cursor must be a 1-element int64 CUDA tensor")
+    lib = _capi.load_library()
+    need = lib.damvs_fusion_cloud_scratch(H, W)
+    if need < 0:
+        check(need)
+    if scratch is None:
+        scratch = torch.empty(need, device=dev, dtype=torch.int32)
+    elif not (ok(scratch, torch.int32, None) and scratch.numel() >= need):
+        raise ValueError("scratch must be a contiguous int32 CUDA tensor of at least %d elements" % need)
+    capacity = records.numel() // RECORD_BYTES
+    check(lib.damvs_fusion_cloud(_capi.stream_ptr(dev), H, W, mask.data_ptr(), xyz.data_ptr(), rgb.data_ptr(),
+                                 scratch.data_ptr(), scratch.numel(), records.data_ptr() if capacity else None, capacity,
+                                 cursor.data_ptr()))
+    return scratch
 
 
 def _save_mask(path, m):
@@ -119,3 +169,60 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0
     rgb = np.concatenate(cols) if cols else np.zeros((0, 3), np.uint8)
     mvsio.write_ply(plyfilename, xyz, rgb)
     return len(xyz)
+
+
+def fuse_scene(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25,
+               rel_diff_base=1 / 1300, device="cuda", method="dypcd", thres_view=5, save_masks=True, max_points=None):
+    """filter_depth's files in, filter_depth's files out, with the scene kept on the device: every view's depth map,
+    camera and (for reference views) three confidences and image are read and uploaded once; each reference view
+    runs the fusion kernel and compact_cloud appends its coloured points to one record buffer behind one device
+    cursor, with no host synchronisation between views; the masks come back only for the PNGs (save_masks) and the
+    cloud in one copy of count * 15 bytes, written by mvsio.write_ply_records.
+    The buffer holds the sum of H * W over the reference views (an exact upper bound) or max_points if that is less;
+    a scene that needs more raises ValueError with the count needed and writes no PLY. Returns the point count."""
+    from PIL import Image
+    if method not in METHODS:
+        raise ValueError("fusion method %r not in %s" % (method, METHODS))
+    pairs = mvsio.read_pair_file(os.path.join(pair_folder, "pair.txt"))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    pfm = lambda kind, v, sfx="": up(mvsio.read_pfm(os.path.join(out_folder, kind, "%08d%s.pfm" % (v, sfx)))[0])
+    cams, depths, confs, rgbs = {}, {}, {}, {}
+    for ref_view, src_views in pairs:
+        for v in [ref_view] + src_views:
+            if v not in depths:
+                cams[v] = mvsio.read_camera_parameters(os.path.join(scan_folder, "cams", "%08d_cam.txt" % v))
+                depths[v] = pfm("depth_est", v)
+        if ref_view not in confs:
+            confs[ref_view] = (pfm("confidence", ref_view), pfm("confidence", ref_view, "_stage2"),
+                               pfm("confidence", ref_view, "_stage1"))
+            img = np.array(Image.open(os.path.join(scan_folder, "images", "%08d.jpg" % ref_view)))
+            if img.dtype != np.uint8 or img.shape != tuple(depths[ref_view].shape) + (3,):
+                raise ValueError("image of view %d: %s %s, expected uint8 %s" % (
+                    ref_view, img.dtype, img.shape, tuple(depths[ref_view].shape) + (3,)))
+            rgbs[ref_view] = up(img)
+    capacity = sum(depths[r].numel() for r, _ in pairs)
+    if max_points is not None:
+        capacity = max(0, min(capacity, int(max_points)))
+    records = torch.empty(capacity * RECORD_BYTES, device=device, dtype=torch.uint8)
+    cursor = torch.zeros(1, device=device, dtype=torch.int64)
+    scratch, masks = {}, []
+    for ref_view, src_views in pairs:
+        K_ref, E_ref = cams[ref_view]
+        srcs = [(depths[v],) + cams[v] for v in src_views]
+        _, mask, xyz = _fuse_view_raw(depths[ref_view], K_ref, E_ref, srcs, confs[ref_view], conf, dist_base,
+                                      rel_diff_base, True, method, thres_view, 1.0, 0.01)
+        shape = tuple(mask.shape)
+        scratch[shape] = compact_cloud(mask, xyz, rgbs[ref_view], records, cursor, scratch.get(shape))
+        if save_masks:
+            masks.append((ref_view, mask))
+    if save_masks:
+        os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+        for ref_view, mask in masks:
+            m = mask.cpu().numpy()
+            for bit, kind in ((1, "photo"), (2, "geo"), (4, "final")):
+                _save_mask(os.path.join(out_folder, "mask", "%08d_%s.png" % (ref_view, kind)), (m & bit) != 0)
+    count = int(cursor.item())
+    if count > capacity:
+        raise ValueError("the scene's point cloud needs %d points, the record buffer holds %d" % (count, capacity))
+    mvsio.write_ply_records(plyfilename, records[:count * RECORD_BYTES].cpu().numpy())
+    return count

@@ -269,6 +269,15 @@ def save_stage_outputs(outdir, filename, outputs, b=0):
     save_pfm(path("confidence", "_stage1.pfm"), resize_nearest(npy(outputs["stage1"]["photometric_confidence"]), w, h))
 
 
+PLY_RECORD_BYTES = 15  # x, y, z float32 + red, green, blue uint8, packed
+
+
+def _ply_header(n):
+    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+            "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
+            % n).encode("ascii")
+
+
 def write_ply(filename, xyz, rgb):
     """Binary little-endian PLY of vertices (x, y, z float32; red, green, blue uint8), the element
     layout filter/dypcd.py:306-326 writes through plyfile."""
@@ -278,12 +287,21 @@ def write_ply(filename, xyz, rgb):
                                   ("blue", "u1")])
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
-              "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n"
-              % len(v))
     with open(filename, "wb") as f:
-        f.write(header.encode("ascii"))
+        f.write(_ply_header(len(v)))
         f.write(v.tobytes())
+
+
+def write_ply_records(filename, records_bytes):
+    """write_ply's file from vertex records already packed as it packs them (15 bytes each: x, y, z little-endian
+    float32, red, green, blue), e.g. the buffer fusion.compact_cloud fills: bytes, bytearray, memoryview or a uint8
+    numpy array."""
+    data = memoryview(records_bytes).cast("B")
+    if data.nbytes % PLY_RECORD_BYTES:
+        raise ValueError("%d bytes are not a whole number of %d-byte records" % (data.nbytes, PLY_RECORD_BYTES))
+    with open(filename, "wb") as f:
+        f.write(_ply_header(data.nbytes // PLY_RECORD_BYTES))
+        f.write(data)
 
 
 def read_ply(filename):

@@ -318,6 +318,24 @@ int damvs_fusion_view_static(void* stream, int H, int W, int nsrc, const float* 
                              const damvs_fusion_cams* cams, double dist_thr, double rel_thr, int thres_view,
                              float* depth_avg, unsigned char* mask, float* xyz);
 
+/* The point cloud of one fused view (filter/dypcd.py:275-301, xyz[final] / color[final]): the view's final pixels
+ * (mask bit value 4; bits 1 and 2 are ignored), in row-major pixel order, as PLY vertex records of 15 bytes: x, y, z
+ * little-endian float32 from xyz [H][W][3], then red, green, blue from rgb [H][W][3] (the image bytes as decoded: the
+ * reference's (float32(u) / 255 * 255).astype(uint8) is u for all 256 values), packed without padding. Record i of the
+ * view is written at byte (base + i) * 15 of `records`, base = *cursor before the call, if and only if
+ * base + i < capacity; *cursor becomes base + the view's count either way, so a cursor above the capacity says how
+ * many records were needed. capacity 0 only counts (records may then be NULL); records needs no alignment.
+ * Three launches on `stream` (count per tile, one-block scan, scatter), no atomics and no waiting between blocks: the
+ * order is exact and the bytes are reproducible. The cursor is read and written by plain device loads and stores, so
+ * all calls that share a cursor must be enqueued on one stream. scratch: damvs_fusion_cloud_scratch(H, W) unsigned
+ * ints of device memory, free for reuse by the next call on the stream.
+ * Errors (before any device work): a null pointer, scratch_elems too small or capacity < 0 -> DAMVS_E_ARG;
+ * H < 1, W < 1 or H * W >= 2^31 -> DAMVS_E_SHAPE. */
+int damvs_fusion_cloud_scratch(int H, int W);
+int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, const float* xyz, const unsigned char* rgb,
+                       unsigned int* scratch, long long scratch_elems, unsigned char* records, long long capacity,
+                       unsigned long long* cursor);
+
 #ifdef __cplusplus
 }
 #endif

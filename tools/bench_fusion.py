@@ -10,6 +10,13 @@ dynamic rule's restatement and is skipped for it. --repeats N times N back-to-ba
 each (ms_per_view_repeats) with their spread; the headline is their median. --kernel-ab compares the two kernels
 themselves (see kernel_ab).
 
+  python tools/bench_fusion.py --scene [--H 1184 --W 1600 --nsrc 10 --repeats 5 --iters 20 --method dypcd|pcd --out F]
+
+--scene times the scene drivers end to end, files in, PLY out, on one synthetic tree of nsrc + 1 views that each list
+all the others as sources (see scene_bench): filter_depth (per view through the host) against fuse_scene (resident
+maps, GPU-compacted cloud), and the three cloud launches of one view by HIP events. One JSON line each, appended to
+--out when given.
+
 Algorithmic bytes per reference view: 4 B x H x W x (1 ref depth + 3 confidences + nsrc source depths
 (each read once; the 4-tap lookups hit L2) + 4 depth_avg + 1 mask + 12 xyz).
 """
@@ -66,6 +73,106 @@ def kernel_ab(args, depths, K, E, confs):
                       "launches_per_block": args.iters, "ms_per_launch": res}), flush=True)
 
 
+def write_scene_tree(root, H, W, nviews, seed=0):
+    """A filter_depth tree of nviews views of test_fusion.plane_scene, each with all the others as sources: pair.txt,
+    cams/, images/ (lossless PNG bytes under .jpg names; PIL reads by content), depth_est/ and confidence/ PFMs."""
+    from PIL import Image
+    from test_fusion import plane_scene
+    from damvsnet_amd import mvsio
+    depths, K, E, confs, _ = plane_scene(nviews, H=H, W=W, seed=seed)
+    rng = np.random.default_rng(seed + 1)
+    for d in ("cams", "images", "depth_est", "confidence"):
+        os.makedirs(os.path.join(root, d), exist_ok=True)
+    for v in range(nviews):
+        cam = np.zeros((2, 4, 4), np.float32)
+        cam[0], cam[1, :3, :3] = E[v], K[v]
+        mvsio.write_cam(os.path.join(root, "cams", "%08d_cam.txt" % v), cam)
+        img = rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+        Image.fromarray(img).save(os.path.join(root, "images", "%08d.jpg" % v), format="PNG", compress_level=1)
+        mvsio.save_pfm(os.path.join(root, "depth_est", "%08d.pfm" % v), depths[v])
+        for c, sfx in zip(confs, ("", "_stage2", "_stage1")):
+            mvsio.save_pfm(os.path.join(root, "confidence", "%08d%s.pfm" % (v, sfx)), np.roll(c, 97 * v, axis=1))
+    with open(os.path.join(root, "pair.txt"), "w") as f:
+        f.write("%d\n" % nviews)
+        for v in range(nviews):
+            src = [s for s in range(nviews) if s != v]
+            f.write("%d\n%d %s\n" % (v, len(src), " ".join("%d 1.0" % s for s in src)))
+    return depths, K, E, confs
+
+
+def scene_bench(args):
+    """Wall clock of filter_depth and fuse_scene on one tree (median of --repeats runs after one warm-up each, same
+    process, runs interleaved), the PLYs asserted byte-identical; then the cloud launches of one view (count, scan,
+    scatter) timed by HIP events over --iters back-to-back calls. The final-stage confidence threshold is 0.5 instead
+    of the reference's 0.9 so that the uniform random confidences keep about 4 in 10 pixels of the plane."""
+    import tempfile
+    from damvsnet_amd import fusion
+    H, W, nviews = args.H, args.W, args.nsrc + 1
+    conf = (0.1, 0.15, 0.5)
+    lines = []
+    with tempfile.TemporaryDirectory() as root:
+        depths, K, E, confs = write_scene_tree(root, H, W, nviews)
+        ply = {"filter_depth": os.path.join(root, "filter_depth.ply"), "fuse_scene": os.path.join(root, "fuse_scene.ply"),
+               "fuse_scene_no_masks": os.path.join(root, "fuse_scene_no_masks.ply")}
+        kw = dict(conf=conf, method=args.method, thres_view=args.thres_view)
+        run = {"filter_depth": lambda: fusion.filter_depth(root, root, root, ply["filter_depth"], **kw),
+               "fuse_scene": lambda: fusion.fuse_scene(root, root, root, ply["fuse_scene"], **kw),
+               "fuse_scene_no_masks": lambda: fusion.fuse_scene(root, root, root, ply["fuse_scene_no_masks"],
+                                                                save_masks=False, **kw)}
+        times, count = {k: [] for k in run}, {}
+        for r in range(max(5, args.repeats) + 1):  # run 0 is the warm-up
+            for name, f in run.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                count[name] = f()
+                torch.cuda.synchronize()
+                if r:
+                    times[name].append(time.perf_counter() - t0)
+        blobs = {k: open(p, "rb").read() for k, p in ply.items()}
+        assert blobs["filter_depth"] == blobs["fuse_scene"] == blobs["fuse_scene_no_masks"], "the PLY files differ"
+        assert len(set(count.values())) == 1
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        for name in run:
+            lines.append({"metric": "scene wall clock, files in, PLY out", "driver": name, "seconds": round(med[name], 4),
+                          "runs": [round(t, 4) for t in times[name]], "views": nviews, "sources_per_view": args.nsrc,
+                          "shape": [H, W], "method": args.method, "conf": list(conf), "points": count[name],
+                          "ply_bytes": len(blobs[name]), "ply_identical_to_filter_depth": True,
+                          "speedup_vs_filter_depth": round(med["filter_depth"] / med[name], 3)})
+    # the cloud launches of one view, maps resident
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d = [cu(x) for x in depths]
+    _, mask, xyz = fusion._fuse_view_raw(d[0], K[0], E[0], [(d[i], K[i], E[i]) for i in range(1, nviews)],
+                                         [cu(c) for c in confs], conf, 0.25, 1 / 1300, True, args.method,
+                                         args.thres_view, 1.0, 0.01)
+    rgb = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device="cuda")
+    n = int(((mask & 4) != 0).sum().item())
+    records = torch.empty(n * 15, dtype=torch.uint8, device="cuda")
+    cursor = torch.zeros(1, dtype=torch.int64, device="cuda")
+    scratch = fusion.compact_cloud(mask, xyz, rgb, records, cursor)
+    reps = []
+    for _ in range(max(5, args.repeats)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.iters):
+            cursor.zero_()
+            fusion.compact_cloud(mask, xyz, rgb, records, cursor, scratch)
+        e1.record()
+        torch.cuda.synchronize()
+        reps.append(e0.elapsed_time(e1) / args.iters)
+    ms = float(np.median(reps))
+    moved = 2 * H * W + n * (12 + 3) + n * 15 + 3 * 4 * scratch.numel()  # mask twice, kept points in, records out
+    lines.append({"metric": "cloud launches per view (count + scan + scatter, incl. the cursor reset), HIP events",
+                  "ms_per_view": round(ms, 4), "ms_per_view_repeats": [round(r, 4) for r in reps], "shape": [H, W],
+                  "points": n, "kept_fraction": round(n / (H * W), 4), "bytes_moved": moved,
+                  "achieved_GBps": round(moved / ms / 1e6, 1)})
+    for line in lines:
+        print(json.dumps(line), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--H", type=int, default=1184)
@@ -77,7 +184,11 @@ def main():
     ap.add_argument("--thres-view", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--kernel-ab", action="store_true")
+    ap.add_argument("--scene", action="store_true")
+    ap.add_argument("--out", default=None, help="--scene: append the JSON lines to this file")
     args = ap.parse_args()
+    if args.scene:
+        return scene_bench(args)
     from test_fusion import plane_scene
     from damvsnet_amd.fusion import fuse_view
     depths, K, E, confs, img = plane_scene(args.nsrc + 1, H=args.H, W=args.W, seed=0)
