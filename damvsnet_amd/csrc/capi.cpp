@@ -2,17 +2,16 @@
 // stream-ordered orchestration of the per-stage kernels.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
-#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "damvs.h"
 #include "damvs_internal.h"
+#include "weight_pack.h"
 
 using namespace damvs;
 
@@ -41,16 +40,6 @@ int hip_check(hipError_t e, const char* what) {
     if (_rc != DAMVS_OK) return _rc; \
   } while (0)
 
-uint16_t to_bf16(float f) {  // round to nearest even; NaN stays NaN
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-enum LayerKind { CONV_S1 = 0, CONV_S2 = 1, DECONV_S2 = 2 };
-
 struct LayerPlan {
   int kind = 0, cin = 0, cout = 0, mt = 0, nphase = 0;
   ConvPhase ph[kMaxPhases];
@@ -74,7 +63,7 @@ struct damvs_stage {
   int C = 0, base = 0, mode = 0, dtype = 0, device = 0;
   LayerPlan L[10];
   float* prob_w = nullptr;  // device [kd][kh][kw][c]
-  void* prob_pack = nullptr;  // bf16, base 8: prob_mfma_kernel's A operand (pack_prob_rows, damvs_stage_create)
+  void* prob_pack = nullptr;  // bf16, base 8: prob_mfma_kernel's A operand (weight_pack.h pack_prob_rows)
   void* prob_split = nullptr;  // fp32, base 8: the same rows as split-f16 pairs (prob_mfma_kernel<float>)
   float prob_scale = 1.f;      // 2^-k of prob_split
   float k1[32] = {0};
@@ -83,213 +72,21 @@ struct damvs_stage {
 
 namespace {
 
-// Weight tap lists. Conv: t = kd*9 + kh*3 + kw at input offset k-1 (input = q*stride + k - 1).
-// ConvTranspose k3 s2 p1 op1, output parity p per dim: p = 0 -> {k=1 at input q},
-// p = 1 -> {k=0 at input q+1, k=2 at input q}   (from o = 2i - 1 + k).
-void build_phases(LayerPlan& P, int kchunk_k) {
-  auto kch = [&](int ntaps) { return (ntaps * P.cin + kchunk_k - 1) / kchunk_k; };
-  std::memset(P.ph, 0, sizeof(P.ph));
-  if (P.kind != DECONV_S2) {
-    P.nphase = 1;
-    ConvPhase& ph = P.ph[0];
-    ph.ntaps = 27;
-    for (int t = 0; t < 27; ++t) {
-      ph.tap[t][0] = (signed char)(t / 9 - 1);
-      ph.tap[t][1] = (signed char)((t / 3) % 3 - 1);
-      ph.tap[t][2] = (signed char)(t % 3 - 1);
-      ph.tap[t][3] = (signed char)t;  // weight tap index
-    }
-    ph.kchunks = kch(27);
-    return;
-  }
-  P.nphase = 8;
-  const int ks[2][2] = {{1, -1}, {0, 2}};
-  const int off[2][2] = {{0, 0}, {1, 0}};
-  const int cnt[2] = {1, 2};
-  for (int p = 0; p < 8; ++p) {
-    ConvPhase& ph = P.ph[p];
-    ph.pd = (p >> 2) & 1;
-    ph.ph = (p >> 1) & 1;
-    ph.pw = p & 1;
-    int t = 0;
-    for (int a = 0; a < cnt[ph.pd]; ++a)
-      for (int b = 0; b < cnt[ph.ph]; ++b)
-        for (int c = 0; c < cnt[ph.pw]; ++c) {
-          ph.tap[t][0] = (signed char)off[ph.pd][a];
-          ph.tap[t][1] = (signed char)off[ph.ph][b];
-          ph.tap[t][2] = (signed char)off[ph.pw][c];
-          ph.tap[t][3] = (signed char)(ks[ph.pd][a] * 9 + ks[ph.ph][b] * 3 + ks[ph.pw][c]);
-          ++t;
-        }
-    ph.ntaps = t;
-    ph.kchunks = kch(t);
-  }
-}
-
-// Pack BN-folded weights wf[co][ci][27] into A-fragment order:
-//   element ((w_off + s*MT + m) * 64 + lane) * E + e  =  W[co = m*16 + (lane & 15)][k = s*KC + (lane >> 4)*E + e]
-// with k -> (tap t = k / cin, ci = k % cin), zero beyond ntaps / cout.
-template <typename S>
-void pack_layer(LayerPlan& P, const std::vector<float>& wf, int E, std::vector<S>& out, S (*cvt)(float)) {
-  const int KC = 4 * E;
-  int w_off = 0;
-  for (int p = 0; p < P.nphase; ++p) {
-    ConvPhase& ph = P.ph[p];
-    ph.w_off = w_off;
-    for (int s = 0; s < ph.kchunks; ++s)
-      for (int m = 0; m < P.mt; ++m)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < E; ++e) {
-            const int co = m * 16 + (lane & 15);
-            const int k = s * KC + (lane >> 4) * E + e;
-            const int t = k / P.cin, ci = k % P.cin;
-            float v = 0.f;
-            if (co < P.cout && t < ph.ntaps) v = wf[((size_t)co * P.cin + ci) * 27 + (unsigned char)ph.tap[t][3]];
-            out.push_back(cvt(v));
-          }
-    w_off += ph.kchunks * P.mt;
-  }
-}
-
-// Row-pair packing for a stride-1 layer with cout <= 8: the 16 MFMA rows are (r, co) = output rows
-// y + r (r = 0, 1) x 8 channels; K runs over 36 taps (dz, dy' = 0..3, dx) x cin, where dy' is the
-// input row relative to y - 1, so row r sees kernel row ky = dy' - r (zero outside 0..2):
-//   element (s * 64 + lane) * E + e  =  A[row = lane & 15][k = s*KC + (lane >> 4)*E + e].
-template <typename S>
-void pack_layer_pair(const LayerPlan& P, const std::vector<float>& wf, int E, std::vector<S>& out, S (*cvt)(float)) {
-  const int KC = 4 * E;
-  const int nch = (36 * P.cin + KC - 1) / KC;
-  for (int s = 0; s < nch; ++s)
-    for (int lane = 0; lane < 64; ++lane)
-      for (int e = 0; e < E; ++e) {
-        const int row = lane & 15, r = row >> 3, co = row & 7;
-        const int k = s * KC + (lane >> 4) * E + e;
-        const int t2 = k / P.cin, ci = k % P.cin;
-        const int dz = t2 / 12, dy = (t2 / 3) % 4, dx = t2 % 3, ky = dy - r;
-        float v = 0.f;
-        if (t2 < 36 && co < P.cout && ky >= 0 && ky <= 2) v = wf[((size_t)co * P.cin + ci) * 27 + (dz * 3 + ky) * 3 + dx];
-        out.push_back(cvt(v));
-      }
-}
-
-// ConvTranspose k3 s2 (Cout <= 8) as 4 phases (pz, py) whose 16 MFMA rows are the two x parities
-// x 8 channels: x-parity 0 takes kx = 1 at input offset 0, parity 1 takes kx = 2 at offset 0 and
-// kx = 0 at offset +1, so both share the input x-offsets {0, +1} (tap[t][2] = dx, tap[t][3] = the
-// (kz, ky) part of the weight tap). K per phase = nz * ny * 2 * cin; over the 4 phases 18 * cin
-// instead of 27 * cin for the 8 single-parity phases, and no M row is padding.
-void build_phases_xpair(LayerPlan& P, int kchunk_k) {
-  const int ks[2][2] = {{1, -1}, {0, 2}};
-  const int off[2][2] = {{0, 0}, {1, 0}};
-  const int cnt[2] = {1, 2};
-  std::memset(P.ph_pair, 0, sizeof(P.ph_pair));
-  P.nphase_pair = 4;
-  for (int p = 0; p < 4; ++p) {
-    ConvPhase& ph = P.ph_pair[p];
-    ph.pd = (p >> 1) & 1;
-    ph.ph = p & 1;
-    ph.pw = 0;
-    int t = 0;
-    for (int a = 0; a < cnt[ph.pd]; ++a)
-      for (int b = 0; b < cnt[ph.ph]; ++b)
-        for (int dx = 0; dx < 2; ++dx) {
-          ph.tap[t][0] = (signed char)off[ph.pd][a];
-          ph.tap[t][1] = (signed char)off[ph.ph][b];
-          ph.tap[t][2] = (signed char)dx;
-          ph.tap[t][3] = (signed char)(ks[ph.pd][a] * 9 + ks[ph.ph][b] * 3);  // + kx by (row parity, dx)
-          ++t;
-        }
-    ph.ntaps = t;
-    ph.kchunks = (t * P.cin + kchunk_k - 1) / kchunk_k;
-  }
-}
-
-template <typename S>
-void pack_layer_xpair(LayerPlan& P, const std::vector<float>& wf, int E, std::vector<S>& out, S (*cvt)(float)) {
-  const int KC = 4 * E;
-  const int kx_of[2][2] = {{1, -1}, {2, 0}};  // [x parity][dx]
-  int w_off = 0;
-  for (int p = 0; p < P.nphase_pair; ++p) {
-    ConvPhase& ph = P.ph_pair[p];
-    ph.w_off = w_off;
-    for (int s = 0; s < ph.kchunks; ++s)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < E; ++e) {
-          const int row = lane & 15, px = row >> 3, co = row & 7;
-          const int k = s * KC + (lane >> 4) * E + e;
-          const int t = k / P.cin, ci = k % P.cin;
-          float v = 0.f;
-          if (co < P.cout && t < ph.ntaps) {
-            const int kx = kx_of[px][(int)ph.tap[t][2]];
-            if (kx >= 0) v = wf[((size_t)co * P.cin + ci) * 27 + (unsigned char)ph.tap[t][3] + kx];
-          }
-          out.push_back(cvt(v));
-        }
-    w_off += ph.kchunks;
-  }
-}
-
-int upload(const void* host, size_t bytes, void** dev);
-float cvt_f32(float v) { return v; }
-uint16_t cvt_bf16(float v) { return to_bf16(v); }
-
-// fp32 layers compute on split-f16 MFMAs (damvs_device.h, mma_split16): the per-layer exponent k that puts the largest
-// |w| * 2^k in (2^13, 2^14], so every lo piece that matters is a normal f16 (0 for an all-zero layer).
-int split_exponent(const std::vector<float>& w) {
-  float mx = 0.f;
-  for (float v : w) mx = std::max(mx, std::fabs(v));
-  if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-  int e;
-  std::frexp(mx, &e);  // mx = f * 2^e, f in [0.5, 1)
-  return 14 - e;
-}
-// A fragments packed as fp32 (4 values per lane and chunk) -> [hi0..hi3 | lo0..lo3] f16 of w * 2^k
-std::vector<uint16_t> split_weights(const std::vector<float>& pk, int k) {
-  std::vector<uint16_t> out(pk.size() * 2);
-  for (size_t q = 0; q < pk.size() / 4; ++q)
-    for (int e = 0; e < 4; ++e) {
-      const float v = std::ldexp(pk[q * 4 + e], k);
-      const _Float16 hi = (_Float16)v;
-      const _Float16 lo = (_Float16)(v - (float)hi);
-      std::memcpy(&out[q * 8 + e], &hi, 2);
-      std::memcpy(&out[q * 8 + 4 + e], &lo, 2);
-    }
-  return out;
-}
-// 32-K packing (8 values per lane and chunk, pack_2d at kchunk_k 32) -> per (chunk, cout tile): [hi: 64 lanes x 8 f16]
-// [lo: 64 lanes x 8 f16] of w * 2^k (conv2d_wide_kernel<float>, WideForm<float>)
-std::vector<uint16_t> split_weights_blocked(const std::vector<float>& pk, int k) {
-  std::vector<uint16_t> out(pk.size() * 2);
-  for (size_t blk = 0; blk < pk.size() / 512; ++blk)
-    for (int lane = 0; lane < 64; ++lane)
-      for (int e = 0; e < 8; ++e) {
-        const float v = std::ldexp(pk[blk * 512 + lane * 8 + e], k);
-        const _Float16 hi = (_Float16)v;
-        const _Float16 lo = (_Float16)(v - (float)hi);
-        std::memcpy(&out[blk * 1024 + lane * 8 + e], &hi, 2);
-        std::memcpy(&out[blk * 1024 + 512 + lane * 8 + e], &lo, 2);
-      }
-  return out;
-}
-int upload_split(const std::vector<float>& pk, int k, void** dev) {
-  const std::vector<uint16_t> h = split_weights(pk, k);
-  return upload(h.data(), h.size() * 2, dev);
-}
-
+// Weight packing is host arithmetic in weight_pack.h; this unit validates, uploads what it returns and launches.
 int fold_bn(const damvs_bn& bn, int c, std::vector<float>& scale, std::vector<float>& shift) {
   if (!bn.weight || !bn.bias || !bn.running_mean || !bn.running_var) return fail(DAMVS_E_ARG, "null BatchNorm tensor");
-  scale.resize(c);
-  shift.resize(c);
-  for (int i = 0; i < c; ++i) {
-    const double inv = 1.0 / std::sqrt((double)bn.running_var[i] + (double)bn.eps);
-    scale[i] = (float)(inv * bn.weight[i]);
-    shift[i] = (float)(bn.bias[i] - bn.running_mean[i] * inv * bn.weight[i]);
-  }
+  bn_affine(bn, c, scale, shift);
   return DAMVS_OK;
 }
 
 int upload(const void* host, size_t bytes, void** dev) {
   if (hipMalloc(dev, bytes) != hipSuccess) return fail(DAMVS_E_NOMEM, "hipMalloc(%zu) failed", bytes);
   return hip_check(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice), "hipMemcpy H2D");
+}
+// a packing of weight_pack.h, when the layer has it (*dev stays null otherwise)
+template <typename T, typename D>
+int upload(const std::vector<T>& v, D** dev) {
+  return v.empty() ? DAMVS_OK : upload(v.data(), v.size() * sizeof(T), reinterpret_cast<void**>(dev));
 }
 
 struct Shapes {
@@ -530,7 +327,6 @@ int damvs_stage_create(const damvs_costreg_params* cr, const damvs_aggweight_par
   st->mode = agg_mode;
   st->dtype = dtype;
   (void)hipGetDevice(&st->device);
-  const int E = dtype == DAMVS_BF16 ? 8 : 4;
   // (cin, cout, kind) of conv0..conv6, conv7, conv9, conv11
   const int spec[10][3] = {{C, b, CONV_S1},         {b, 2 * b, CONV_S2},     {2 * b, 2 * b, CONV_S1},
                            {2 * b, 4 * b, CONV_S2}, {4 * b, 4 * b, CONV_S1}, {4 * b, 8 * b, CONV_S2},
@@ -542,9 +338,6 @@ int damvs_stage_create(const damvs_costreg_params* cr, const damvs_aggweight_par
     P.cin = spec[li][0];
     P.cout = spec[li][1];
     P.kind = spec[li][2];
-    P.mt = (P.cout + 15) / 16;
-    if (P.mt == 3) P.mt = 4;
-    build_phases(P, 4 * E);
     std::vector<float> scale, shift;
     rc = fold_bn(cr->bn[li], P.cout, scale, shift);
     if (rc != DAMVS_OK) break;
@@ -557,126 +350,29 @@ int damvs_stage_create(const damvs_costreg_params* cr, const damvs_aggweight_par
           const float v = P.kind == DECONV_S2 ? W[((size_t)ci * P.cout + co) * 27 + t] : W[((size_t)co * P.cin + ci) * 27 + t];
           wf[((size_t)co * P.cin + ci) * 27 + t] = v * scale[co];
         }
-    const int kexp = dtype == DAMVS_BF16 ? 0 : split_exponent(wf);
-    P.wscale = std::ldexp(1.f, -kexp);
-    if (P.kind == DECONV_S2 && P.cout == 8) {
-      // conv11 runs on its x-pair packing alone (wpack_pair below; conv_args): no 8-phase packing
-    } else if (dtype == DAMVS_BF16) {
-      std::vector<uint16_t> pk;
-      pack_layer<uint16_t>(P, wf, E, pk, cvt_bf16);
-      rc = upload(pk.data(), pk.size() * 2, &P.wpack);
-    } else {
-      std::vector<float> pk;
-      pack_layer<float>(P, wf, E, pk, cvt_f32);
-      rc = upload_split(pk, kexp, &P.wpack);
-    }
-    if (rc == DAMVS_OK && dtype != DAMVS_BF16 &&
-        ((P.kind == CONV_S1 && P.cin == 16 && P.cout == 16) || (P.kind == DECONV_S2 && P.cin == 32 && P.cout == 16) ||
-         (P.kind == CONV_S2 && P.cin == 8 && P.cout == 16))) {
-      // the z-streamed kernels of conv2, conv9 and conv1 (fp32 split-f16 forms): the plain packing at 32 K per chunk
-      LayerPlan P32 = P;
-      build_phases(P32, 32);
-      std::vector<float> p32;
-      pack_layer<float>(P32, wf, 8, p32, cvt_f32);
-      const std::vector<uint16_t> h = split_weights_blocked(p32, kexp);
-      rc = upload(h.data(), h.size() * 2, &P.wpack32);
-      P.wgat32 = P.wpack32;  // the same plain 32-K packing serves the gather kernel
-      for (int p = 0; p < P32.nphase; ++p) P.k32_chunks[p] = P32.ph[p].kchunks, P.k32_off[p] = P32.ph[p].w_off;
-    } else if (rc == DAMVS_OK && dtype != DAMVS_BF16 && P.cout > 8) {
-      // the gather kernel's 32-K form (conv3d_mfma_kernel<float, MT, false, true>: 16x16x32 f16 split products, twice the
-      // 16-K form's MFMA rate) for the layers that run on it (conv3, conv5, conv6, conv7 and the tile kernels' fallbacks)
-      LayerPlan P32 = P;
-      build_phases(P32, 32);
-      std::vector<float> p32;
-      pack_layer<float>(P32, wf, 8, p32, cvt_f32);
-      const std::vector<uint16_t> h = split_weights_blocked(p32, kexp);
-      rc = upload(h.data(), h.size() * 2, &P.wgat32);
-      for (int p = 0; p < P32.nphase; ++p) P.k32_chunks[p] = P32.ph[p].kchunks, P.k32_off[p] = P32.ph[p].w_off;
-    }
-    if (rc == DAMVS_OK && P.kind == DECONV_S2 && P.cout <= 8) {
-      build_phases_xpair(P, 4 * E);
-      if (dtype == DAMVS_BF16) {
-        std::vector<uint16_t> pk;
-        pack_layer_xpair<uint16_t>(P, wf, E, pk, cvt_bf16);
-        rc = upload(pk.data(), pk.size() * 2, &P.wpack_pair);
-      } else {
-        std::vector<float> pk;
-        pack_layer_xpair<float>(P, wf, E, pk, cvt_f32);
-        rc = upload_split(pk, kexp, &P.wpack_pair);
-        if (rc == DAMVS_OK && P.cin == 16 && P.cout == 8) {  // conv11's z-streamed kernel (deconv_xpair_zslide<float>)
-          LayerPlan P32 = P;
-          build_phases_xpair(P32, 32);
-          std::vector<float> p32;
-          pack_layer_xpair<float>(P32, wf, 8, p32, cvt_f32);
-          const std::vector<uint16_t> h = split_weights_blocked(p32, kexp);
-          rc = upload(h.data(), h.size() * 2, &P.wpack32);
-        }
-      }
-    }
-    if (rc == DAMVS_OK && P.kind == CONV_S1 && P.cout <= 8) {
-      if (dtype == DAMVS_BF16) {
-        std::vector<uint16_t> pk;
-        pack_layer_pair<uint16_t>(P, wf, E, pk, cvt_bf16);
-        rc = upload(pk.data(), pk.size() * 2, &P.wpack_pair);
-      } else {
-        std::vector<float> pk;
-        pack_layer_pair<float>(P, wf, E, pk, cvt_f32);
-        rc = upload_split(pk, kexp, &P.wpack_pair);
-        if (rc == DAMVS_OK) {  // conv0's z-streamed kernel (conv3d_zslide_pair<float>, CIN 8 / 16 / 32)
-          std::vector<float> p32;
-          pack_layer_pair<float>(P, wf, 8, p32, cvt_f32);
-          const std::vector<uint16_t> h = split_weights_blocked(p32, kexp);
-          rc = upload(h.data(), h.size() * 2, &P.wpack32);
-        }
-      }
-    }
-    if (rc == DAMVS_OK) rc = upload(shift.data(), shift.size() * 4, reinterpret_cast<void**>(&P.bias));
+    const CostregPack k = pack_costreg_layer(P.cin, P.cout, P.kind, dtype, wf);
+    P.mt = k.mt; P.wscale = k.wscale; P.nphase = k.ph.n; P.nphase_pair = k.ph_pair.n;
+    std::memcpy(P.ph, k.ph.ph, sizeof(P.ph));
+    std::memcpy(P.ph_pair, k.ph_pair.ph, sizeof(P.ph_pair));
+    std::memcpy(P.k32_chunks, k.k32_chunks, sizeof(P.k32_chunks));
+    std::memcpy(P.k32_off, k.k32_off, sizeof(P.k32_off));
+    rc = upload(k.wpack, &P.wpack);
+    if (rc == DAMVS_OK) rc = upload(k.wpack_pair, &P.wpack_pair);
+    if (rc == DAMVS_OK) rc = upload(k.wpack32, &P.wpack32);
+    if (rc == DAMVS_OK) rc = upload(k.wgat32, &P.wgat32);
+    if (rc == DAMVS_OK && k.wgat32_is_wpack32) P.wgat32 = P.wpack32;
+    if (rc == DAMVS_OK) rc = upload(shift, &P.bias);
   }
   if (rc == DAMVS_OK) {
     std::vector<float> pw((size_t)27 * b);  // [kd][kh][kw][c] from [1][c][kd][kh][kw]
     for (int c = 0; c < b; ++c)
       for (int t = 0; t < 27; ++t) pw[(size_t)t * b + c] = cr->prob_weight[(size_t)c * 27 + t];
-    rc = upload(pw.data(), pw.size() * 4, reinterpret_cast<void**>(&st->prob_w));
+    rc = upload(pw, &st->prob_w);
   }
-  if (rc == DAMVS_OK && dtype == DAMVS_BF16 && b == 8) {
-    // pack_prob_rows: the prob conv (Conv3d(8, 1, k3), models/module.py:530) as prob_mfma_kernel's A operand
-    // (k_regress.hip): rows m = 4 j + dz (output pixel row j of four, kernel depth dz), K = (voxel slot
-    // sl = 3 r + kx of input row r = 0..5, channel), entry W[c][dz][ky = r - j][kx] when dz < 3, sl < 18 and
-    // 0 <= ky <= 2, else 0; [chunk][term][lane][8], the fp32 weight as kProbRowTerms bf16 terms (hi + lo).
-    std::vector<uint16_t> pk((size_t)kProbRowChunks * kProbRowTerms * 64 * 8, 0);
-    for (int k = 0; k < kProbRowChunks; ++k)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 8; ++e) {
-          const int m = lane & 15, j = m >> 2, dz = m & 3, sl = 4 * k + (lane >> 4), r = sl / 3, kx = sl % 3;
-          const int ky = r - j;
-          float v = 0.f;
-          if (dz < 3 && sl < 18 && ky >= 0 && ky <= 2) v = cr->prob_weight[(size_t)e * 27 + dz * 9 + ky * 3 + kx];
-          for (int t = 0; t < kProbRowTerms; ++t) {
-            const uint16_t q = to_bf16(v);
-            pk[(((size_t)k * kProbRowTerms + t) * 64 + lane) * 8 + e] = q;
-            float qf;
-            const uint32_t qb = (uint32_t)q << 16;
-            std::memcpy(&qf, &qb, 4);
-            v -= qf;  // exact: the remainder of a round-to-nearest bf16 term
-          }
-        }
-    rc = upload(pk.data(), pk.size() * 2, &st->prob_pack);
-  }
-  if (rc == DAMVS_OK && dtype == DAMVS_F32 && b == 8) {
-    // the rows of pack_prob_rows (above) with fp32 weights, split-f16 at 32 K per chunk: prob_mfma_kernel<float>
-    std::vector<float> pf((size_t)kProbRowChunks * 64 * 8, 0.f), all(cr->prob_weight, cr->prob_weight + 27 * 8);
-    for (int k = 0; k < kProbRowChunks; ++k)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 8; ++e) {
-          const int m = lane & 15, j = m >> 2, dz = m & 3, sl = 4 * k + (lane >> 4), r = sl / 3, kx = sl % 3;
-          const int ky = r - j;
-          if (dz < 3 && sl < 18 && ky >= 0 && ky <= 2)
-            pf[((size_t)k * 64 + lane) * 8 + e] = cr->prob_weight[(size_t)e * 27 + dz * 9 + ky * 3 + kx];
-        }
-    const int kp = split_exponent(all);
-    st->prob_scale = std::ldexp(1.f, -kp);
-    const std::vector<uint16_t> hsp = split_weights_blocked(pf, kp);
-    rc = upload(hsp.data(), hsp.size() * 2, &st->prob_split);
+  if (rc == DAMVS_OK && b == 8) {  // prob_mfma_kernel's A operand in the stage's storage type
+    const ProbRows pr = pack_prob_rows(cr->prob_weight, dtype, kProbRowChunks, kProbRowTerms);
+    st->prob_scale = pr.scale;
+    rc = upload(pr.rows, dtype == DAMVS_BF16 ? &st->prob_pack : &st->prob_split);
   }
   if (rc == DAMVS_OK && agg_mode == DAMVS_AGG_ADAPTIVE) {
     std::vector<float> sc1, sh1, sc2, sh2;
@@ -970,7 +666,7 @@ int damvs_sparse_depth_pyramid(void* stream, int B, int h, int w, const float* d
 struct damvs_conv2d {
   damvs_conv2d_desc d;
   int dtype = 0, cout_pad = 0, cout_store = 0, MTtot = 0, nphase = 0, kchunk_k = 0;
-  int xpair = 0;  // x-parity-pair phases (build_phases_2d_xpair / pack_2d_xpair)
+  int xpair = 0;  // x-parity-pair phases (weight_pack.h build_phases_2d / XPair2dElem)
   float wscale = 1.f;  // fp32: 2^-k of the split-f16 weights (split_weights)
   Conv2dPhase ph[4];
   void* wpack = nullptr;
@@ -981,156 +677,6 @@ struct damvs_conv2d {
 };
 
 namespace {
-
-// Tap lists. Conv: input = q*s + (k - p), one phase. Transposed conv of stride s: output parity r
-// per dim takes the kernel taps k with (r + p - k) % s == 0 at input offset (r + p - k) / s.
-int build_phases_2d(damvs_conv2d* L) {
-  const damvs_conv2d_desc& d = L->d;
-  const int K = d.kernel, s = d.stride, p = d.padding;
-  const int ctot = d.c0 + d.c1;
-  std::memset(L->ph, 0, sizeof(L->ph));
-  std::vector<int> offs[2], ks[2];  // per parity r
-  if (!d.transposed) {
-    L->nphase = 1;
-    for (int k = 0; k < K; ++k) { offs[0].push_back(k - p); ks[0].push_back(k); }
-  } else {
-    if (s != 1 && s != 2) return fail(DAMVS_E_SHAPE, "transposed stride %d unsupported", s);
-    L->nphase = s * s;
-    // taps in ascending input offset: a stride-1 transposed conv then has exactly the tap list of a plain conv
-    // (offsets -p .. K-1-p, row-major), so the LDS-tiled 3x3 kernel (lds3_ok) takes the full-resolution decoder
-    // layers instead of the gather kernel
-    for (int r = 0; r < s; ++r)
-      for (int k = K - 1; k >= 0; --k)
-        if (((r + p - k) % s + s) % s == 0) { offs[r].push_back((r + p - k) / s); ks[r].push_back(k); }
-  }
-  int w_off = 0, g_off = 0;
-  for (int ph = 0; ph < L->nphase; ++ph) {
-    Conv2dPhase& P = L->ph[ph];
-    const int ry = d.transposed ? ph / s : 0, rx = d.transposed ? ph % s : 0;
-    P.py = ry;
-    P.px = rx;
-    int t = 0;
-    for (size_t a = 0; a < offs[ry].size(); ++a)
-      for (size_t b = 0; b < offs[rx].size(); ++b) {
-        if (t >= 25) return fail(DAMVS_E_SHAPE, "more than 25 taps per phase");
-        P.tap[t][0] = (signed char)offs[ry][a];
-        P.tap[t][1] = (signed char)offs[rx][b];
-        P.wtap[t] = (signed char)(ks[ry][a] * K + ks[rx][b]);
-        ++t;
-      }
-    P.ntaps = t;
-    P.kchunks = ctot > 0 ? (t * ctot + L->kchunk_k - 1) / L->kchunk_k : 0;
-    P.gchunks = d.ngeo > 0 ? (t * d.ngeo + L->kchunk_k - 1) / L->kchunk_k : 0;
-    P.w_off = w_off;
-    P.g_off = g_off;
-    w_off += P.kchunks + P.gchunks;
-    g_off += t * d.ngeo;
-  }
-  return DAMVS_OK;
-}
-
-// ConvTranspose2d stride 2 with cout = 8 as 2 phases (output row parity ry): the 16 MFMA rows are
-// (output x parity px, channel), and the taps are (input row offsets of ry) x (the union of the input
-// x offsets of both parities). A row whose parity does not use an x offset gets zero weights. Per
-// output pixel pair this is |offs[ry]| * |union| taps instead of |offs[ry]| * (|offs[0]| + |offs[1]|)
-// over two phases with half the MFMA rows empty, and the 16 channels of an x pair are one 32-byte
-// store. wtap keeps the ky * K part; pack_2d_xpair resolves kx per row parity.
-int build_phases_2d_xpair(damvs_conv2d* L) {
-  const damvs_conv2d_desc& d = L->d;
-  const int K = d.kernel, p = d.padding;
-  std::memset(L->ph, 0, sizeof(L->ph));
-  std::vector<int> offs[2], ks[2];
-  for (int r = 0; r < 2; ++r)
-    for (int k = 0; k < K; ++k)
-      if (((r + p - k) % 2 + 2) % 2 == 0) { offs[r].push_back((r + p - k) / 2); ks[r].push_back(k); }
-  std::vector<int> xo;  // union of x offsets over both parities, ascending
-  for (int r = 0; r < 2; ++r)
-    for (int o : offs[r])
-      if (std::find(xo.begin(), xo.end(), o) == xo.end()) xo.push_back(o);
-  std::sort(xo.begin(), xo.end());
-  L->nphase = 2;
-  int w_off = 0;
-  for (int ry = 0; ry < 2; ++ry) {
-    Conv2dPhase& P = L->ph[ry];
-    P.py = ry;
-    P.px = 0;
-    int t = 0;
-    for (size_t a = 0; a < offs[ry].size(); ++a)
-      for (int dx : xo) {
-        if (t >= 25) return fail(DAMVS_E_SHAPE, "more than 25 taps per phase");
-        P.tap[t][0] = (signed char)offs[ry][a];
-        P.tap[t][1] = (signed char)dx;
-        P.wtap[t] = (signed char)(ks[ry][a] * K);
-        ++t;
-      }
-    P.ntaps = t;
-    P.kchunks = (t * (d.c0 + d.c1) + L->kchunk_k - 1) / L->kchunk_k;
-    P.gchunks = 0;
-    P.w_off = w_off;
-    w_off += P.kchunks;
-  }
-  return DAMVS_OK;
-}
-
-float wget(const damvs_conv2d_desc& d, const float* W, int co, int wc, int wt) {
-  const int KK = d.kernel * d.kernel;
-  return d.transposed ? W[((size_t)wc * d.cout + co) * KK + wt] : W[((size_t)co * d.cin + wc) * KK + wt];
-}
-
-template <typename S>
-void pack_2d(const damvs_conv2d* L, const float* W, std::vector<S>& out, S (*cvt)(float)) {
-  const damvs_conv2d_desc& d = L->d;
-  const int E = L->kchunk_k / 4, ctot = d.c0 + d.c1;
-  for (int ph = 0; ph < L->nphase; ++ph) {
-    const Conv2dPhase& P = L->ph[ph];
-    // tensor-input chunks (K = tap x concatenated channel), then plane chunks (K = tap x plane)
-    for (int s = 0; s < P.kchunks + P.gchunks; ++s)
-      for (int m = 0; m < L->MTtot; ++m)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int e = 0; e < E; ++e) {
-            const int co = m * 16 + (lane & 15);
-            const bool plane = s >= P.kchunks;
-            const int k = (plane ? s - P.kchunks : s) * L->kchunk_k + (lane >> 4) * E + e;
-            const int per = plane ? d.ngeo : ctot;
-            const int t = k / per, ci = k % per;
-            float v = 0.f;
-            if (co < d.cout && t < P.ntaps) {
-              const int wc = plane ? d.geo_at[ci] : ci < d.c0 ? d.c0_at + ci : d.c1_at + (ci - d.c0);
-              v = wget(d, W, co, wc, (unsigned char)P.wtap[t]);
-            }
-            out.push_back(cvt(v));
-          }
-  }
-}
-
-// A rows = (x parity px = row >> 3, channel co = row & 7); kx from the parity's tap list.
-template <typename S>
-void pack_2d_xpair(const damvs_conv2d* L, const float* W, std::vector<S>& out, S (*cvt)(float)) {
-  const damvs_conv2d_desc& d = L->d;
-  const int E = L->kchunk_k / 4, ctot = d.c0 + d.c1, K = d.kernel, p = d.padding;
-  auto kx_of = [&](int px, int dx) {
-    for (int k = 0; k < K; ++k)
-      if (((px + p - k) % 2 + 2) % 2 == 0 && (px + p - k) / 2 == dx) return k;
-    return -1;
-  };
-  for (int ph = 0; ph < L->nphase; ++ph) {
-    const Conv2dPhase& P = L->ph[ph];
-    for (int s = 0; s < P.kchunks; ++s)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < E; ++e) {
-          const int row = lane & 15, px = row >> 3, co = row & 7;
-          const int k = s * L->kchunk_k + (lane >> 4) * E + e;
-          const int t = k / ctot, ci = k % ctot;
-          float v = 0.f;
-          if (co < d.cout && t < P.ntaps) {
-            const int kx = kx_of(px, P.tap[t][1]);
-            const int wc = ci < d.c0 ? d.c0_at + ci : d.c1_at + (ci - d.c0);
-            if (kx >= 0) v = wget(d, W, co, wc, (unsigned char)P.wtap[t] + kx);
-          }
-          out.push_back(cvt(v));
-        }
-  }
-}
 
 void conv2d_out(const damvs_conv2d* L, int Hi, int Wi, int* Ho, int* Wo) {
   const damvs_conv2d_desc& d = L->d;
@@ -1163,61 +709,24 @@ int damvs_conv2d_create(const damvs_conv2d_desc* desc, const float* weight, cons
     return fail(DAMVS_E_SHAPE, "at most one fp32 plane next to tensor inputs (got %d)", d.ngeo);
   if (d.c0 + d.c1 == 0 && d.cout > 16)
     return fail(DAMVS_E_SHAPE, "plane-only layers support cout <= 16 (got %d)", d.cout);
+  const Conv2dPack k = pack_conv2d(d, weight, dtype);
+  if (!k.err.empty()) return fail(DAMVS_E_SHAPE, "%s", k.err.c_str());
   damvs_conv2d* L = new damvs_conv2d();
   L->d = d;
   L->dtype = dtype;
   L->kchunk_k = 4 * E;
-  L->MTtot = (d.cout + 15) / 16;
-  L->cout_pad = L->MTtot * 16;
-  L->cout_store = (d.cout + 3) / 4 * 4;
-  L->xpair = d.transposed && d.stride == 2 && d.cout == 8 && d.ngeo == 0 && d.c0 + d.c1 > 0;
-  int rc = L->xpair ? build_phases_2d_xpair(L) : build_phases_2d(L);
-  if (rc == DAMVS_OK && d.c0 + d.c1 + d.ngeo > 0) {
-    if (dtype == DAMVS_BF16) {
-      std::vector<uint16_t> pk;
-      if (L->xpair) pack_2d_xpair<uint16_t>(L, weight, pk, cvt_bf16);
-      else pack_2d<uint16_t>(L, weight, pk, cvt_bf16);
-      rc = upload(pk.data(), pk.size() * 2, &L->wpack);
-    } else {
-      std::vector<float> pk;
-      if (L->xpair) pack_2d_xpair<float>(L, weight, pk, cvt_f32);
-      else pack_2d<float>(L, weight, pk, cvt_f32);
-      const int kexp = split_exponent(pk);
-      L->wscale = std::ldexp(1.f, -kexp);
-      rc = upload_split(pk, kexp, &L->wpack);
-      // the 32-K split form of the wide kernel (conv2d_wide_kernel<float>), of the narrow halo kernel
-      // (conv2d_halo_kernel<float, ..., W32>) and of the gather kernel (conv2d_mfma_kernel<float, ..., K32>: channel
-      // counts in multiples of 8): phases and weights at 32 K per chunk
-      const int ctot = d.c0 + d.c1;
-      if (rc == DAMVS_OK && !L->xpair && d.c0 % 8 == 0 && d.c1 % 8 == 0 && ctot >= 8 && d.ngeo <= 1) {
-        damvs_conv2d T32 = *L;
-        T32.wpack = nullptr;
-        T32.kchunk_k = 32;
-        rc = build_phases_2d(&T32);
-        if (rc == DAMVS_OK) {
-          std::vector<float> p32;
-          pack_2d<float>(&T32, weight, p32, cvt_f32);
-          const std::vector<uint16_t> h = split_weights_blocked(p32, kexp);
-          rc = upload(h.data(), h.size() * 2, &L->wpack32);
-          std::memcpy(L->ph32, T32.ph, sizeof(L->ph32));
-        }
-      }
-    }
-  }
-  if (rc == DAMVS_OK && d.ngeo > 0) {
-    std::vector<float> wg;
-    for (int ph = 0; ph < L->nphase; ++ph)
-      for (int t = 0; t < L->ph[ph].ntaps; ++t)
-        for (int g = 0; g < d.ngeo; ++g)
-          for (int co = 0; co < L->cout_pad; ++co)
-            wg.push_back(co < d.cout ? wget(d, weight, co, d.geo_at[g], (unsigned char)L->ph[ph].wtap[t]) : 0.f);
-    rc = upload(wg.data(), wg.size() * 4, reinterpret_cast<void**>(&L->wgeo));
-  }
+  L->MTtot = k.MTtot; L->cout_pad = k.cout_pad; L->cout_store = k.cout_store;
+  L->xpair = k.xpair; L->nphase = k.nphase; L->wscale = k.wscale;
+  std::memcpy(L->ph, k.ph, sizeof(L->ph));
+  std::memcpy(L->ph32, k.ph32, sizeof(L->ph32));
+  int rc = upload(k.wpack, &L->wpack);
+  if (rc == DAMVS_OK) rc = upload(k.wpack32, &L->wpack32);
+  if (rc == DAMVS_OK) rc = upload(k.wgeo, &L->wgeo);
   if (rc == DAMVS_OK) {
     std::vector<float> b(L->cout_pad, 0.f);
     if (bias)
       for (int i = 0; i < d.cout; ++i) b[i] = bias[i];
-    rc = upload(b.data(), b.size() * 4, reinterpret_cast<void**>(&L->bias));
+    rc = upload(b, &L->bias);
   }
   if (rc != DAMVS_OK) {
     damvs_conv2d_destroy(L);
@@ -1261,6 +770,91 @@ int damvs_conv2d_border_bias(void* stream, int dtype, int B, int H, int W, int c
                    "border_bias launch");
 }
 
+int damvs_conv2d_destroy(damvs_conv2d* L) {
+  if (!L) return DAMVS_OK;
+  if (L->wpack) (void)hipFree(L->wpack);
+  if (L->wpack32) (void)hipFree(L->wpack32);
+  if (L->wgeo) (void)hipFree(L->wgeo);
+  if (L->bias) (void)hipFree(L->bias);
+  delete L;
+  return DAMVS_OK;
+}
+
+int damvs_conv2d_out_size(const damvs_conv2d* L, int Hi, int Wi, int* Ho, int* Wo, int* cout_stored) {
+  if (!L || !Ho || !Wo) return fail(DAMVS_E_ARG, "null argument");
+  conv2d_out(L, Hi, Wi, Ho, Wo);
+  if (cout_stored) *cout_stored = L->cout_store;
+  return DAMVS_OK;
+}
+
+int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int Wi, const void* in0,
+                         const void* in1, const float* const* geo, const long long* geo_batch_stride, const void* res_pre,
+                         const void* res_post, int post_up, void* out) {
+  if (!L || !out) return fail(DAMVS_E_ARG, "null argument");
+  const damvs_conv2d_desc& d = L->d;
+  if ((d.c0 > 0 && !in0) || (d.c1 > 0 && !in1)) return fail(DAMVS_E_ARG, "missing tensor input");
+  if (d.ngeo > 0 && (!geo || !geo_batch_stride)) return fail(DAMVS_E_ARG, "missing geometry planes");
+  if (B < 1 || Hi < 1 || Wi < 1) return fail(DAMVS_E_SHAPE, "bad shape");
+  if (res_post && post_up != 1 && post_up != 2) return fail(DAMVS_E_ARG, "post_up must be 1 or 2");
+  Conv2dArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.in0 = in0;
+  a.in1 = in1;
+  a.c0 = d.c0;
+  a.c1 = d.c1;
+  a.ngeo = d.ngeo;
+  for (int g = 0; g < d.ngeo; ++g) {
+    if (!geo[g]) return fail(DAMVS_E_ARG, "null geometry plane %d", g);
+    a.geo[g] = geo[g];
+    a.geo_bstride[g] = geo_batch_stride[g];
+  }
+  a.wpack = L->wpack;
+  a.wgeo = L->wgeo;
+  a.bias = L->bias;
+  a.res_pre = res_pre;
+  a.res_post = res_post;
+  a.post_up = res_post ? post_up : 1;
+  a.out = out;
+  a.cout = L->cout_store;
+  a.cout_pad = L->cout_pad;
+  a.MTtot = L->MTtot;
+  a.B = B;
+  a.Hi = Hi;
+  a.Wi = Wi;
+  conv2d_out(L, Hi, Wi, &a.Ho, &a.Wo);
+  if (a.Ho < 1 || a.Wo < 1) return fail(DAMVS_E_SHAPE, "empty output");
+  if (d.transposed) {
+    if (a.Ho != d.stride * Hi || a.Wo != d.stride * Wi)
+      return fail(DAMVS_E_SHAPE, "transposed conv must produce stride x input size");
+    a.Hq = Hi;
+    a.Wq = Wi;
+    a.in_stride = 1;
+    a.out_stride = d.stride;
+  } else {
+    a.Hq = a.Ho;
+    a.Wq = a.Wo;
+    a.in_stride = d.stride;
+    a.out_stride = 1;
+  }
+  if (res_post && (a.Ho % a.post_up || a.Wo % a.post_up)) return fail(DAMVS_E_SHAPE, "bad upsample shape");
+  a.relu = d.relu;
+  a.wscale = L->wscale;
+  a.nphase = L->nphase;
+  a.xpair = L->xpair;
+  a.div_wq = make_fastdiv(a.Wq);
+  a.div_hq = make_fastdiv(a.Hq);
+  std::memcpy(a.ph, L->ph, sizeof(a.ph));
+  Conv2dArgs a32 = a;
+  if (L->wpack32) {  // fp32: the same layer on its 32-K split packing (same taps, K chunks of 32)
+    std::memcpy(a32.ph, L->ph32, sizeof(a32.ph));
+    a32.wpack = L->wpack32;
+    a32.wide32 = 1;
+  }
+  return hip_check(launch_conv2d(reinterpret_cast<hipStream_t>(stream), L->dtype, a, L->wpack32 ? &a32 : nullptr),
+                   "conv2d launch");
+}
+
+// ============================================================================ depth fusion
 // Validation and camera / pointer packing shared by the two fusion entry points (the thresholds are theirs).
 static int fusion_pack(int H, int W, int nsrc, const float* depth_ref, const float* const* depth_src,
                        const float* const* conf, const float* conf_thr, const damvs_fusion_cams* cams, float* depth_avg,
@@ -1348,90 +942,6 @@ int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, co
   a.capacity = capacity;
   a.cursor = cursor;
   return hip_check(launch_fusion_cloud(static_cast<hipStream_t>(stream), a), "fusion_cloud launch");
-}
-
-int damvs_conv2d_destroy(damvs_conv2d* L) {
-  if (!L) return DAMVS_OK;
-  if (L->wpack) (void)hipFree(L->wpack);
-  if (L->wpack32) (void)hipFree(L->wpack32);
-  if (L->wgeo) (void)hipFree(L->wgeo);
-  if (L->bias) (void)hipFree(L->bias);
-  delete L;
-  return DAMVS_OK;
-}
-
-int damvs_conv2d_out_size(const damvs_conv2d* L, int Hi, int Wi, int* Ho, int* Wo, int* cout_stored) {
-  if (!L || !Ho || !Wo) return fail(DAMVS_E_ARG, "null argument");
-  conv2d_out(L, Hi, Wi, Ho, Wo);
-  if (cout_stored) *cout_stored = L->cout_store;
-  return DAMVS_OK;
-}
-
-int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int Wi, const void* in0,
-                         const void* in1, const float* const* geo, const long long* geo_batch_stride, const void* res_pre,
-                         const void* res_post, int post_up, void* out) {
-  if (!L || !out) return fail(DAMVS_E_ARG, "null argument");
-  const damvs_conv2d_desc& d = L->d;
-  if ((d.c0 > 0 && !in0) || (d.c1 > 0 && !in1)) return fail(DAMVS_E_ARG, "missing tensor input");
-  if (d.ngeo > 0 && (!geo || !geo_batch_stride)) return fail(DAMVS_E_ARG, "missing geometry planes");
-  if (B < 1 || Hi < 1 || Wi < 1) return fail(DAMVS_E_SHAPE, "bad shape");
-  if (res_post && post_up != 1 && post_up != 2) return fail(DAMVS_E_ARG, "post_up must be 1 or 2");
-  Conv2dArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.in0 = in0;
-  a.in1 = in1;
-  a.c0 = d.c0;
-  a.c1 = d.c1;
-  a.ngeo = d.ngeo;
-  for (int g = 0; g < d.ngeo; ++g) {
-    if (!geo[g]) return fail(DAMVS_E_ARG, "null geometry plane %d", g);
-    a.geo[g] = geo[g];
-    a.geo_bstride[g] = geo_batch_stride[g];
-  }
-  a.wpack = L->wpack;
-  a.wgeo = L->wgeo;
-  a.bias = L->bias;
-  a.res_pre = res_pre;
-  a.res_post = res_post;
-  a.post_up = res_post ? post_up : 1;
-  a.out = out;
-  a.cout = L->cout_store;
-  a.cout_pad = L->cout_pad;
-  a.MTtot = L->MTtot;
-  a.B = B;
-  a.Hi = Hi;
-  a.Wi = Wi;
-  conv2d_out(L, Hi, Wi, &a.Ho, &a.Wo);
-  if (a.Ho < 1 || a.Wo < 1) return fail(DAMVS_E_SHAPE, "empty output");
-  if (d.transposed) {
-    if (a.Ho != d.stride * Hi || a.Wo != d.stride * Wi)
-      return fail(DAMVS_E_SHAPE, "transposed conv must produce stride x input size");
-    a.Hq = Hi;
-    a.Wq = Wi;
-    a.in_stride = 1;
-    a.out_stride = d.stride;
-  } else {
-    a.Hq = a.Ho;
-    a.Wq = a.Wo;
-    a.in_stride = d.stride;
-    a.out_stride = 1;
-  }
-  if (res_post && (a.Ho % a.post_up || a.Wo % a.post_up)) return fail(DAMVS_E_SHAPE, "bad upsample shape");
-  a.relu = d.relu;
-  a.wscale = L->wscale;
-  a.nphase = L->nphase;
-  a.xpair = L->xpair;
-  a.div_wq = make_fastdiv(a.Wq);
-  a.div_hq = make_fastdiv(a.Hq);
-  std::memcpy(a.ph, L->ph, sizeof(a.ph));
-  Conv2dArgs a32 = a;
-  if (L->wpack32) {  // fp32: the same layer on its 32-K split packing (same taps, K chunks of 32)
-    std::memcpy(a32.ph, L->ph32, sizeof(a32.ph));
-    a32.wpack = L->wpack32;
-    a32.wide32 = 1;
-  }
-  return hip_check(launch_conv2d(reinterpret_cast<hipStream_t>(stream), L->dtype, a, L->wpack32 ? &a32 : nullptr),
-                   "conv2d launch");
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "conv_phases.h"
 #include "switches.h"
 #include "warp_tiles.h"
 
@@ -26,7 +27,6 @@ constexpr int kMaxViews = 16;
 constexpr int kAmaxReps = 32;    // replicas per slot (one 128-byte line each): atomics spread over 32 addresses
 constexpr int kAmaxStride = 32;  // words between replicas
 constexpr int kAmaxSlotWords = kAmaxReps * kAmaxStride;
-constexpr int kMaxPhases = 8;
 
 // ---------------------------------------------------------------- warp + aggregation
 struct WarpArgs {
@@ -66,16 +66,7 @@ __device__ __forceinline__ int fdiv(const FastDiv& f, int n) {
 #endif
 
 // ---------------------------------------------------------------- MFMA implicit-GEMM conv3d
-// A "phase" is one regular sub-convolution: for an iteration-grid point q,
-//   input  coord = q * in_stride + tap_offset        (zero outside the input)
-//   output coord = q * out_stride + (pd, ph, pw)
-// Conv3d k3 s1/s2 has one phase with 27 taps; ConvTranspose3d k3 s2 p1 op1 is 8 phases of
-// 1..8 taps each (sub-pixel decomposition), so no MFMA work is spent on structural zeros.
-struct ConvPhase {
-  int ntaps, kchunks, w_off, pd, ph, pw;
-  signed char tap[27][4];  // dz, dy, dx, (pad)
-};
-
+// phases: ConvPhase, conv_phases.h
 struct ConvArgs {
   const void* in;
   void* out;
@@ -108,16 +99,7 @@ struct ConvArgs {
 };
 
 // ---------------------------------------------------------------- 2D front-end convolutions
-// One phase of a 2D conv / transposed conv: input = q * in_stride + tap offset, output =
-// q * out_stride + (py, px). Weights for the tensor inputs are packed like the 3D kernel's
-// (A-fragment order, K = taps x (c0 + c1)); geometry-plane weights are fp32 [tap][g][cout_pad].
-struct Conv2dPhase {
-  int ntaps, kchunks, gchunks, w_off, g_off, py, px;  // kchunks: tensor-input K chunks; gchunks: plane K chunks
-  signed char tap[25][2];  // dy, dx (up to 5 x 5)
-  signed char wtap[25];    // weight tap index ky*k + kx
-  signed char pad_[3];
-};
-
+// phases: Conv2dPhase, conv_phases.h
 struct Conv2dArgs {
   const void* in0;
   const void* in1;

@@ -233,7 +233,7 @@ BN_COMBOS = ((0.5, 1.0), (1.0, 1.0), (2.0, 1.0), (0.5, 0.25), (1.0, 0.25), (1.0,
 
 
 def fold_bn_numpy(weight, bias, mean, var, eps):
-    """capi.cpp fold_bn restated: float32 tensors and a float32 eps in, double arithmetic, float32 scale / shift out."""
+    """weight_pack.h bn_affine restated: float32 tensors and a float32 eps in, double arithmetic, float32 scale / shift out."""
     weight, bias, mean, var = (np.asarray(t, np.float32).astype(np.float64) for t in (weight, bias, mean, var))
     inv = 1.0 / np.sqrt(var + np.float64(np.float32(eps)))
     return (inv * weight).astype(np.float32), (bias - mean * inv * weight).astype(np.float32)

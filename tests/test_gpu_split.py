@@ -2,7 +2,7 @@
 against float64 references on inputs whose f16 lo pieces are not zero, so the gate is still equality per element.
 
 The fp32 path computes w * x as wl*xh + wh*xl + wh*xh on f16 MFMAs (damvs_device.h mma_split16 / mma_split32), weights
-split on the host (capi.cpp split_weights), activations in the kernels after the power-of-two prescale. On the fixtures
+split on the host (weight_pack.h split_weights), activations in the kernels after the power-of-two prescale. On the fixtures
 of test_gpu_lattice.py every lo piece is 0, so the two cross terms never count there. The "two-piece" fixtures here add
 +-2^-12 (random sign) to the non-zero lattice values of
 
@@ -56,7 +56,7 @@ def two_piece(t, dim, parity, gen):
 
 
 def split_exponent(v):
-    """capi.cpp split_exponent and damvs_device.h prescale_from_max alike: the k that puts max |v| * 2^k in [2^13, 2^14)."""
+    """weight_pack.h split_exponent and damvs_device.h prescale_from_max alike: the k that puts max |v| * 2^k in [2^13, 2^14)."""
     mx = float(v.abs().max())
     return 0 if mx == 0.0 else max(-100, min(100, 14 - math.frexp(mx)[1]))
 
@@ -191,10 +191,10 @@ def conv2d_split_fixture(i):
 
 def is_xpair(case):
     tr, k, s, p, op, c0, c1, geo, cout = case[:9]
-    return tr and s == 2 and cout == 8 and not geo          # capi.cpp damvs_conv2d_create
+    return tr and s == 2 and cout == 8 and not geo          # weight_pack.h pack_conv2d
 
 
-# The rows DAMVS_CONV2D_G32=0 can reroute are those with a 32-K split packing (capi.cpp damvs_conv2d_create) that
+# The rows DAMVS_CONV2D_G32=0 can reroute are those with a 32-K split packing (weight_pack.h pack_conv2d) that
 # conv2d_route leaves to the gather kernel; the packing's condition alone is stated here, so a row that the wide, halo or
 # LDS kernels take runs its usual kernel once more. DAMVS_PLANES_MFMA=0 reroutes the plane-only rows.
 G32_ROWS = [i for i, c in enumerate(CONV2D_CASES)
@@ -274,7 +274,7 @@ FIXTURE_GROUPS = (["conv2d", "fpn_top", "bn_fold"] + ["unet_C%d_%dx%dx%d" % ((C,
 @pytest.mark.parametrize("group", FIXTURE_GROUPS)
 def test_two_piece_fixtures_are_exact(group):
     """Every case of the GPU tests below meets the conditions of check_two_piece, with the f16 pieces taken as the code
-    takes them (hi = f16(v), lo = f16(v - hi); weights times the folded scale and the layer's 2^k of capi.cpp
+    takes them (hi = f16(v), lo = f16(v - hi); weights times the folded scale and the layer's 2^k of weight_pack.h
     split_exponent; U-Net activations times each batch element's prescale). The FPN top's packed weight halves are
     those of the lattice fixture (lo = 0). The zero-shift net folds to the lattice scales and a shift of exactly 0."""
     if group == "conv2d":

@@ -137,7 +137,7 @@ def compose_rt(B, N, h, w):
 
 
 def fold_bn(weight, bias, mean, var, eps):
-    """capi.cpp fold_bn, operation for operation (double arithmetic, one rounding to float32 per value)."""
+    """weight_pack.h bn_affine, operation for operation (double arithmetic, one rounding to float32 per value)."""
     inv = 1.0 / np.sqrt(np.float64(np.float32(var)) + np.float64(np.float32(eps)))
     w, b, m = (np.float64(np.float32(t)) for t in (weight, bias, mean))
     return np.float32(inv * w), np.float32(b - m * inv * w)
