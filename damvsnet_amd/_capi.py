@@ -108,6 +108,7 @@ SIGNATURES = (
     ("damvs_conv2d_forward", c_int, (c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                      ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_longlong), c_void_p, c_void_p,
                                      c_int, c_void_p)),
+    ("damvs_conv2d_route", c_int, (c_void_p, c_int, c_int, c_int, ctypes.c_char_p, c_size_t)),
     ("damvs_fusion_view", c_int, (c_void_p, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_void_p),
                                   ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(DamvsFusionCams),
                                   ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p)),

@@ -787,34 +787,19 @@ int damvs_conv2d_out_size(const damvs_conv2d* L, int Hi, int Wi, int* Ho, int* W
   return DAMVS_OK;
 }
 
-int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int Wi, const void* in0,
-                         const void* in1, const float* const* geo, const long long* geo_batch_stride, const void* res_pre,
-                         const void* res_post, int post_up, void* out) {
-  if (!L || !out) return fail(DAMVS_E_ARG, "null argument");
+// The layer's launch arguments at one size: everything conv2d_route reads (shapes, phases, packings, weights), on top
+// of the operand pointers the caller has put into the zeroed `a`. a32: the fp32 layer's 32-K split packing, when it
+// has one (L->wpack32). Shared by the forward and the route query, so both route on the same Conv2dArgs.
+static int conv2d_args(const damvs_conv2d* L, int B, int Hi, int Wi, Conv2dArgs& a, Conv2dArgs& a32) {
   const damvs_conv2d_desc& d = L->d;
-  if ((d.c0 > 0 && !in0) || (d.c1 > 0 && !in1)) return fail(DAMVS_E_ARG, "missing tensor input");
-  if (d.ngeo > 0 && (!geo || !geo_batch_stride)) return fail(DAMVS_E_ARG, "missing geometry planes");
   if (B < 1 || Hi < 1 || Wi < 1) return fail(DAMVS_E_SHAPE, "bad shape");
-  if (res_post && post_up != 1 && post_up != 2) return fail(DAMVS_E_ARG, "post_up must be 1 or 2");
-  Conv2dArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.in0 = in0;
-  a.in1 = in1;
   a.c0 = d.c0;
   a.c1 = d.c1;
   a.ngeo = d.ngeo;
-  for (int g = 0; g < d.ngeo; ++g) {
-    if (!geo[g]) return fail(DAMVS_E_ARG, "null geometry plane %d", g);
-    a.geo[g] = geo[g];
-    a.geo_bstride[g] = geo_batch_stride[g];
-  }
   a.wpack = L->wpack;
   a.wgeo = L->wgeo;
   a.bias = L->bias;
-  a.res_pre = res_pre;
-  a.res_post = res_post;
-  a.post_up = res_post ? post_up : 1;
-  a.out = out;
+  if (!a.res_post) a.post_up = 1;
   a.cout = L->cout_store;
   a.cout_pad = L->cout_pad;
   a.MTtot = L->MTtot;
@@ -836,7 +821,7 @@ int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int
     a.in_stride = d.stride;
     a.out_stride = 1;
   }
-  if (res_post && (a.Ho % a.post_up || a.Wo % a.post_up)) return fail(DAMVS_E_SHAPE, "bad upsample shape");
+  if (a.res_post && (a.Ho % a.post_up || a.Wo % a.post_up)) return fail(DAMVS_E_SHAPE, "bad upsample shape");
   a.relu = d.relu;
   a.wscale = L->wscale;
   a.nphase = L->nphase;
@@ -844,14 +829,58 @@ int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int
   a.div_wq = make_fastdiv(a.Wq);
   a.div_hq = make_fastdiv(a.Hq);
   std::memcpy(a.ph, L->ph, sizeof(a.ph));
-  Conv2dArgs a32 = a;
+  a32 = a;
   if (L->wpack32) {  // fp32: the same layer on its 32-K split packing (same taps, K chunks of 32)
     std::memcpy(a32.ph, L->ph32, sizeof(a32.ph));
     a32.wpack = L->wpack32;
     a32.wide32 = 1;
   }
+  return DAMVS_OK;
+}
+
+int damvs_conv2d_forward(const damvs_conv2d* L, void* stream, int B, int Hi, int Wi, const void* in0,
+                         const void* in1, const float* const* geo, const long long* geo_batch_stride, const void* res_pre,
+                         const void* res_post, int post_up, void* out) {
+  if (!L || !out) return fail(DAMVS_E_ARG, "null argument");
+  const damvs_conv2d_desc& d = L->d;
+  if ((d.c0 > 0 && !in0) || (d.c1 > 0 && !in1)) return fail(DAMVS_E_ARG, "missing tensor input");
+  if (d.ngeo > 0 && (!geo || !geo_batch_stride)) return fail(DAMVS_E_ARG, "missing geometry planes");
+  if (B < 1 || Hi < 1 || Wi < 1) return fail(DAMVS_E_SHAPE, "bad shape");
+  if (res_post && post_up != 1 && post_up != 2) return fail(DAMVS_E_ARG, "post_up must be 1 or 2");
+  Conv2dArgs a, a32;
+  std::memset(&a, 0, sizeof(a));
+  a.in0 = in0;
+  a.in1 = in1;
+  for (int g = 0; g < d.ngeo; ++g) {
+    if (!geo[g]) return fail(DAMVS_E_ARG, "null geometry plane %d", g);
+    a.geo[g] = geo[g];
+    a.geo_bstride[g] = geo_batch_stride[g];
+  }
+  a.res_pre = res_pre;
+  a.res_post = res_post;
+  a.post_up = post_up;
+  a.out = out;
+  DAMVS_TRY(conv2d_args(L, B, Hi, Wi, a, a32));
   return hip_check(launch_conv2d(reinterpret_cast<hipStream_t>(stream), L->dtype, a, L->wpack32 ? &a32 : nullptr),
                    "conv2d launch");
+}
+
+int damvs_conv2d_route(const damvs_conv2d* L, int B, int Hi, int Wi, char* buf, size_t n) {
+  if (!L || !buf || n == 0) return fail(DAMVS_E_ARG, "null argument");
+  buf[0] = 0;
+  Conv2dArgs a, a32;
+  std::memset(&a, 0, sizeof(a));
+  // the forward's arguments but for the operand pointers, which no router reads; the planes as the front-end passes
+  // them: 16-byte aligned, one image apart (the plane-only kernels' vector forms ask for that)
+  for (int g = 0; g < L->d.ngeo; ++g) a.geo_bstride[g] = (long long)Hi * Wi;
+  DAMVS_TRY(conv2d_args(L, B, Hi, Wi, a, a32));
+  Conv2dReport rep = {buf, n, 0};
+  if (launch_conv2d(nullptr, L->dtype, a, L->wpack32 ? &a32 : nullptr, &rep) != hipSuccess || rep.len == 0) {
+    buf[0] = 0;
+    return fail(DAMVS_E_SHAPE, "no conv2d kernel takes this layer at B %d, %d x %d", B, Hi, Wi);
+  }
+  if (rep.len >= n) return fail(DAMVS_E_ARG, "route buffer of %zu bytes too small for %zu characters", n, rep.len);
+  return DAMVS_OK;
 }
 
 // ============================================================================ depth fusion

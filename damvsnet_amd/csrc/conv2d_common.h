@@ -2,10 +2,26 @@
 // NHWC load / store and the epilogue tail (residual before ReLU, ReLU, residual after ReLU, store).
 #pragma once
 
+#include <cstdio>
+
 #include "damvs_device.h"
 
 namespace damvs {
 namespace {
+
+// The route report of a launcher (Conv2dReport, damvs_internal.h): the kernel's name as the demangler prints it,
+// "base<T, targs...>" with T spelled "float" / "unsigned short" (bf16_t), then " grid=(x,y)". Called from the branch
+// that launches, with the template arguments and the grid of that launch.
+inline int put_targ(char* p, size_t n, bool v) { return std::snprintf(p, n, ", %s", v ? "true" : "false"); }
+inline int put_targ(char* p, size_t n, int v) { return std::snprintf(p, n, ", %d", v); }
+template <typename T, typename... A>
+hipError_t report_kernel(Conv2dReport* rep, const char* base, dim3 grid, A... targs) {
+  char name[160];
+  size_t l = (size_t)std::snprintf(name, sizeof(name), "%s<%s", base, sizeof(T) == 2 ? "unsigned short" : "float");
+  ((l += (size_t)put_targ(name + l, sizeof(name) - l, targs)), ...);
+  rep->len = (size_t)std::snprintf(rep->buf, rep->n, "%s> grid=(%u,%u)", name, grid.x, grid.y);
+  return hipSuccess;
+}
 
 template <typename T>
 __device__ __forceinline__ void ld4(const T* p, float* r);

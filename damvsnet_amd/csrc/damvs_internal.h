@@ -145,9 +145,16 @@ hipError_t launch_block_channels(hipStream_t s, int store, const FeatPtrs& src, 
 hipError_t launch_conv3d(hipStream_t s, int store, const ConvArgs& a);
 // a: the layer on its 16-K packing (bf16: its only one); a32: the same fp32 layer on its 32-K split packing (a32->wide32
 // set), or nullptr when it has none. conv2d_route (k_conv2d.hip) picks the kernel and the packing.
-hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a, const Conv2dArgs* a32);
+// rep: instead of launching, the launcher that would launch writes "<kernel><template arguments> grid=(x,y)" into
+// rep->buf (damvs_conv2d_route; report_kernel, conv2d_common.h). No HIP call is made then.
+struct Conv2dReport {
+  char* buf;
+  size_t n;    // bytes of buf
+  size_t len;  // characters of the whole report (>= n: it did not fit); 0 when no launcher was reached
+};
+hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a, const Conv2dArgs* a32, Conv2dReport* rep = nullptr);
 // layers whose only inputs are fp32 planes (c0 = c1 = 0), on the VALU (k_planes.hip)
-hipError_t launch_conv2d_planes(hipStream_t s, int store, const Conv2dArgs& a);
+hipError_t launch_conv2d_planes(hipStream_t s, int store, const Conv2dArgs& a, Conv2dReport* rep = nullptr);
 struct BorderArgs {
   float corr[9 * 16];  // [tap][channel] of a 3x3 conv, channels < 16
 };

@@ -1058,7 +1058,7 @@ __global__ __launch_bounds__(256) void conv2d_halo_kernel(const Conv2dArgs a, in
 }
 
 template <typename T, int MT, int WM, bool W32 = false, bool RS = false>
-hipError_t launch_halo_t(hipStream_t s, const Conv2dArgs& a, int dmin, int span) {
+hipError_t launch_halo_t(hipStream_t s, const Conv2dArgs& a, int dmin, int span, Conv2dReport* rep) {
   constexpr int KC = W32 ? 32 : 4 * Stor<T>::E;
   const int tx = (a.Wq + HGC - 1) / HGC, ty = (a.Hq + HGR - 1) / HGR;
   const int nsl = (a.c0 + a.c1) / KC;
@@ -1066,6 +1066,7 @@ hipError_t launch_halo_t(hipStream_t s, const Conv2dArgs& a, int dmin, int span)
   const size_t smem = W32 ? hp * 8 * 16 : (nsl > 1 ? 2 : 1) * hp * 4 * 16;  // one slice (or W32): one buffer
   const long long nblk = (long long)tx * ty * a.B * a.nphase;
   const dim3 grid((unsigned)nblk, (unsigned)(a.MTtot / (MT * WM)));
+  if (rep) return report_kernel<T>(rep, "conv2d_halo_kernel", grid, MT, WM, a.c1 > 0, W32, RS);
   auto k = a.c1 > 0 ? conv2d_halo_kernel<T, MT, WM, true, W32, RS> : conv2d_halo_kernel<T, MT, WM, false, W32, RS>;
   return launch_big_lds(k, grid, dim3(256), smem, s, a, tx, ty, nsl, dmin, span);
 }
@@ -1118,19 +1119,19 @@ bool halo_route(const Conv2dArgs& a, int KC, bool w32, bool bf16, Conv2dRoute& r
 }
 
 template <typename T>
-hipError_t launch_halo(hipStream_t s, const Conv2dArgs& a, const Conv2dRoute& r) {
+hipError_t launch_halo(hipStream_t s, const Conv2dArgs& a, const Conv2dRoute& r, Conv2dReport* rep) {
   if constexpr (sizeof(T) == 4) {
     if (r.k32) {
-      if (r.mt == 2) return r.rs ? launch_halo_t<T, 2, 1, true, true>(s, a, r.dmin, r.span) : launch_halo_t<T, 2, 1, true>(s, a, r.dmin, r.span);
-      return r.rs ? launch_halo_t<T, 1, 1, true, true>(s, a, r.dmin, r.span) : launch_halo_t<T, 1, 1, true>(s, a, r.dmin, r.span);
+      if (r.mt == 2) return r.rs ? launch_halo_t<T, 2, 1, true, true>(s, a, r.dmin, r.span, rep) : launch_halo_t<T, 2, 1, true>(s, a, r.dmin, r.span, rep);
+      return r.rs ? launch_halo_t<T, 1, 1, true, true>(s, a, r.dmin, r.span, rep) : launch_halo_t<T, 1, 1, true>(s, a, r.dmin, r.span, rep);
     }
   }
-  if (r.wm == 2) return launch_halo_t<T, 4, 2>(s, a, r.dmin, r.span);
+  if (r.wm == 2) return launch_halo_t<T, 4, 2>(s, a, r.dmin, r.span, rep);
   switch (r.mt) {
-    case 8: return launch_halo_t<T, 8, 1>(s, a, r.dmin, r.span);
-    case 4: return launch_halo_t<T, 4, 1>(s, a, r.dmin, r.span);
-    case 2: return launch_halo_t<T, 2, 1>(s, a, r.dmin, r.span);
-    default: return launch_halo_t<T, 1, 1>(s, a, r.dmin, r.span);
+    case 8: return launch_halo_t<T, 8, 1>(s, a, r.dmin, r.span, rep);
+    case 4: return launch_halo_t<T, 4, 1>(s, a, r.dmin, r.span, rep);
+    case 2: return launch_halo_t<T, 2, 1>(s, a, r.dmin, r.span, rep);
+    default: return launch_halo_t<T, 1, 1>(s, a, r.dmin, r.span, rep);
   }
 }
 
@@ -1832,11 +1833,12 @@ size_t wide_smem(W, int span) {
 }
 
 template <typename T, typename W>
-hipError_t launch_wide_t(hipStream_t s, const Conv2dArgs& a, W w, int dmin, int span) {
+hipError_t launch_wide_t(hipStream_t s, const Conv2dArgs& a, W w, int dmin, int span, Conv2dReport* rep) {
   const int tx = (a.Wq + WC - 1) / WC, ty = (a.Hq + W::WRT - 1) / W::WRT;
   const int nsl = (a.c0 + a.c1) / 32;
   const long long nblk = (long long)tx * ty * a.B * a.nphase;
   const dim3 grid((unsigned)nblk, (unsigned)(a.MTtot / (4 * W::WM)));
+  if (rep) return report_kernel<T>(rep, "conv2d_wide_kernel", grid, a.c1 > 0, W::IS, W::WM, W::RS, W::R1);
   auto k = a.c1 > 0 ? conv2d_wide_kernel<T, true, W::IS, W::WM, W::RS, W::R1> : conv2d_wide_kernel<T, false, W::IS, W::WM, W::RS, W::R1>;
   return launch_big_lds(k, grid, dim3(256), wide_smem<T>(w, span), s, a, tx, ty, nsl, dmin, span);
 }
@@ -1895,8 +1897,8 @@ bool wide_route(const Conv2dArgs& a, bool f32, Conv2dRoute& r) {
 }
 
 template <typename T>
-hipError_t launch_wide(hipStream_t s, const Conv2dArgs& a, const Conv2dRoute& r) {
-  return with_wide_form<sizeof(T) == 4>(a.in_stride, r, [&](auto w) { return launch_wide_t<T>(s, a, w, r.dmin, r.span); });
+hipError_t launch_wide(hipStream_t s, const Conv2dArgs& a, const Conv2dRoute& r, Conv2dReport* rep) {
+  return with_wide_form<sizeof(T) == 4>(a.in_stride, r, [&](auto w) { return launch_wide_t<T>(s, a, w, r.dmin, r.span, rep); });
 }
 
 // conv2d_xpair_lds_kernel's layers: x-pair phases of a 16-channel single-input transposed stride-2 conv whose taps
@@ -1929,9 +1931,10 @@ bool lds3_ok(const Conv2dArgs& a) {
 }
 
 template <typename T, int CIN, int MT>
-hipError_t launch_lds2_t(hipStream_t s, const Conv2dArgs& a) {
+hipError_t launch_lds2_t(hipStream_t s, const Conv2dArgs& a, Conv2dReport* rep) {
   const int tx = (a.Wo + L2W - 1) / L2W, ty = (a.Ho + L2H - 1) / L2H;
   const long long nt = (long long)tx * ty * a.B;
+  if (rep) return report_kernel<T>(rep, "conv2d_lds_kernel", dim3((unsigned)nt), CIN, MT);
   hipLaunchKernelGGL((conv2d_lds_kernel<T, CIN, MT>), dim3((unsigned)nt), dim3(256), 0, s, a, tx, ty, (int)nt);
   return hipGetLastError();
 }
@@ -1945,13 +1948,13 @@ bool lds3_route(const Conv2dArgs& a, bool f32) {
 }
 
 template <typename T>
-hipError_t launch_lds3(hipStream_t s, const Conv2dArgs& a) {
+hipError_t launch_lds3(hipStream_t s, const Conv2dArgs& a, Conv2dReport* rep) {
   const int MT = a.MTtot;
   if constexpr (sizeof(T) == 2) {
-    if (a.c0 == 32) return MT == 1 ? launch_lds2_t<T, 32, 1>(s, a) : launch_lds2_t<T, 32, 2>(s, a);
+    if (a.c0 == 32) return MT == 1 ? launch_lds2_t<T, 32, 1>(s, a, rep) : launch_lds2_t<T, 32, 2>(s, a, rep);
   }
-  if (a.c0 == 8) return MT == 1 ? launch_lds2_t<T, 8, 1>(s, a) : launch_lds2_t<T, 8, 2>(s, a);
-  return MT == 1 ? launch_lds2_t<T, 16, 1>(s, a) : launch_lds2_t<T, 16, 2>(s, a);
+  if (a.c0 == 8) return MT == 1 ? launch_lds2_t<T, 8, 1>(s, a, rep) : launch_lds2_t<T, 8, 2>(s, a, rep);
+  return MT == 1 ? launch_lds2_t<T, 16, 1>(s, a, rep) : launch_lds2_t<T, 16, 2>(s, a, rep);
 }
 
 
@@ -1966,9 +1969,10 @@ bool lds_s2_ok(const Conv2dArgs& a) {
 }
 
 template <typename T, int CIN, int MT, int TR>
-hipError_t launch_lds_s2_t(hipStream_t s, const Conv2dArgs& a) {
+hipError_t launch_lds_s2_t(hipStream_t s, const Conv2dArgs& a, Conv2dReport* rep) {
   const int tx = (a.Wo + S2W - 1) / S2W, ty = (a.Ho + TR - 1) / TR;
   const long long nt = (long long)tx * ty * a.B;
+  if (rep) return report_kernel<T>(rep, "conv2d_lds_s2_kernel", dim3((unsigned)nt), CIN, MT, TR);
   hipLaunchKernelGGL((conv2d_lds_s2_kernel<T, CIN, MT, TR>), dim3((unsigned)nt), dim3(256), 0, s, a, tx, ty, (int)nt);
   return hipGetLastError();
 }
@@ -1978,19 +1982,20 @@ bool lds_s2_route(const Conv2dArgs& a) { return lds_s2_ok(a) && a.MTtot <= 2 && 
 
 // Tile rows: 4 (LDS <= 47 KB), 2 for fp32 CIN 16 (59 KB).
 template <typename T>
-hipError_t launch_lds_s2(hipStream_t s, const Conv2dArgs& a) {
+hipError_t launch_lds_s2(hipStream_t s, const Conv2dArgs& a, Conv2dReport* rep) {
   const bool m2 = a.MTtot == 2;
   constexpr bool SP = sizeof(T) == 4;
-  if (a.c0 == 8) return m2 ? launch_lds_s2_t<T, 8, 2, 4>(s, a) : launch_lds_s2_t<T, 8, 1, 4>(s, a);
-  return m2 ? launch_lds_s2_t<T, 16, 2, SP ? 2 : 4>(s, a) : launch_lds_s2_t<T, 16, 1, SP ? 2 : 4>(s, a);
+  if (a.c0 == 8) return m2 ? launch_lds_s2_t<T, 8, 2, 4>(s, a, rep) : launch_lds_s2_t<T, 8, 1, 4>(s, a, rep);
+  return m2 ? launch_lds_s2_t<T, 16, 2, SP ? 2 : 4>(s, a, rep) : launch_lds_s2_t<T, 16, 1, SP ? 2 : 4>(s, a, rep);
 }
 
 
 template <typename T, int MT, bool K32 = false>
-hipError_t launch_mt(hipStream_t s, const Conv2dArgs& a) {
+hipError_t launch_mt(hipStream_t s, const Conv2dArgs& a, Conv2dReport* rep) {
   const long long Qtot = (long long)a.B * a.Hq * a.Wq;
   const int nq = (int)((Qtot + 4LL * kG2 * 16 - 1) / (4LL * kG2 * 16));
   dim3 grid((unsigned)(nq * a.nphase), (unsigned)((a.MTtot + MT - 1) / MT));
+  if (rep) return report_kernel<T>(rep, "conv2d_mfma_kernel", grid, MT, a.c1 > 0, false, K32);
   if (a.c1 > 0)
     hipLaunchKernelGGL((conv2d_mfma_kernel<T, MT, true, false, K32>), grid, dim3(256), 0, s, a, nq);
   else
@@ -2060,12 +2065,15 @@ Conv2dRoute conv2d_route(const Conv2dArgs& a, const Conv2dArgs* a32, int store) 
 }
 
 template <typename T>
-hipError_t launch_route(hipStream_t s, const Conv2dRoute& r, const Conv2dArgs& a) {  // a: on the packing r names
+// rep: write the kernel and its grid there and launch nothing (damvs_conv2d_route). Every launcher below reports from
+// the branch that launches, with the template arguments and the grid of that launch.
+hipError_t launch_route(hipStream_t s, const Conv2dRoute& r, const Conv2dArgs& a, Conv2dReport* rep) {  // a: on the packing r names
   switch (r.family) {
-    case Conv2dFamily::planes: return launch_conv2d_planes(s, sizeof(T) == 2 ? ST_BF16 : ST_F32, a);
+    case Conv2dFamily::planes: return launch_conv2d_planes(s, sizeof(T) == 2 ? ST_BF16 : ST_F32, a, rep);
     case Conv2dFamily::xpair_lds: {
       const int tx = (a.Wq + L2W - 1) / L2W, ty = (a.Hq + L2H - 1) / L2H;
       const long long nt = (long long)tx * ty * a.B;
+      if (rep) return report_kernel<T>(rep, "conv2d_xpair_lds_kernel", dim3((unsigned)nt));
       hipLaunchKernelGGL(conv2d_xpair_lds_kernel<T>, dim3((unsigned)nt), dim3(256), 0, s, a, tx, ty, (int)nt);
       return hipGetLastError();
     }
@@ -2073,26 +2081,27 @@ hipError_t launch_route(hipStream_t s, const Conv2dRoute& r, const Conv2dArgs& a
       const long long Qtot = (long long)a.B * a.Hq * a.Wq;
       const int nq = (int)((Qtot + 4LL * kG2 * 16 - 1) / (4LL * kG2 * 16));
       const dim3 grid((unsigned)(nq * a.nphase), 1);
+      if (rep) return report_kernel<T>(rep, "conv2d_mfma_kernel", grid, 1, a.c1 > 0, true, false);
       if (a.c1 > 0)
         hipLaunchKernelGGL((conv2d_mfma_kernel<T, 1, true, true>), grid, dim3(256), 0, s, a, nq);
       else
         hipLaunchKernelGGL((conv2d_mfma_kernel<T, 1, false, true>), grid, dim3(256), 0, s, a, nq);
       return hipGetLastError();
     }
-    case Conv2dFamily::lds3: return launch_lds3<T>(s, a);
-    case Conv2dFamily::lds_s2: return launch_lds_s2<T>(s, a);
-    case Conv2dFamily::halo: return launch_halo<T>(s, a, r);
-    case Conv2dFamily::wide: return launch_wide<T>(s, a, r);
+    case Conv2dFamily::lds3: return launch_lds3<T>(s, a, rep);
+    case Conv2dFamily::lds_s2: return launch_lds_s2<T>(s, a, rep);
+    case Conv2dFamily::halo: return launch_halo<T>(s, a, r, rep);
+    case Conv2dFamily::wide: return launch_wide<T>(s, a, r, rep);
     case Conv2dFamily::gather32:
       if constexpr (sizeof(T) == 4) {
-        if (r.mt == 4) return launch_mt<T, 4, true>(s, a);
-        return r.mt == 2 ? launch_mt<T, 2, true>(s, a) : launch_mt<T, 1, true>(s, a);
+        if (r.mt == 4) return launch_mt<T, 4, true>(s, a, rep);
+        return r.mt == 2 ? launch_mt<T, 2, true>(s, a, rep) : launch_mt<T, 1, true>(s, a, rep);
       }
       return hipErrorInvalidValue;
     case Conv2dFamily::gather:
-      if (r.mt == 8) return launch_mt<T, 8>(s, a);
-      if (r.mt == 4) return launch_mt<T, 4>(s, a);
-      return r.mt == 2 ? launch_mt<T, 2>(s, a) : launch_mt<T, 1>(s, a);
+      if (r.mt == 8) return launch_mt<T, 8>(s, a, rep);
+      if (r.mt == 4) return launch_mt<T, 4>(s, a, rep);
+      return r.mt == 2 ? launch_mt<T, 2>(s, a, rep) : launch_mt<T, 1>(s, a, rep);
     case Conv2dFamily::invalid: break;
   }
   return hipErrorInvalidValue;
@@ -2305,10 +2314,10 @@ hipError_t launch_border_bias(hipStream_t s, int store, const BorderArgs& a, int
   return hipGetLastError();
 }
 
-hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a, const Conv2dArgs* a32) {
+hipError_t launch_conv2d(hipStream_t s, int store, const Conv2dArgs& a, const Conv2dArgs* a32, Conv2dReport* rep) {
   const Conv2dRoute r = conv2d_route(a, a32, store);
   const Conv2dArgs& p = r.k32 ? *a32 : a;
-  return store == ST_BF16 ? launch_route<bf16_t>(s, r, p) : launch_route<float>(s, r, p);
+  return store == ST_BF16 ? launch_route<bf16_t>(s, r, p, rep) : launch_route<float>(s, r, p, rep);
 }
 
 }  // namespace damvs

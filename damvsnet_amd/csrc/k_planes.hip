@@ -363,9 +363,10 @@ bool planes_fast_ok(const Conv2dArgs& a, int K) {
 }
 
 template <typename T, int K>
-hipError_t launch_planes4_k(hipStream_t st, const Conv2dArgs& a) {
+hipError_t launch_planes4_k(hipStream_t st, const Conv2dArgs& a, Conv2dReport* rep) {
   const long long Qtot = (long long)a.B * ((a.Ho + 1) / 2) * (a.Wo / 4);
   dim3 grid((unsigned)((Qtot + 255) / 256));
+  if (rep) return report_kernel<T>(rep, "conv2d_planes4_kernel", grid, 8, K, a.ngeo < 4 ? a.ngeo : 4);
   switch (a.ngeo) {
     case 1: hipLaunchKernelGGL((conv2d_planes4_kernel<T, 8, K, 1>), grid, dim3(256), 0, st, a, a.wgeo); break;
     case 2: hipLaunchKernelGGL((conv2d_planes4_kernel<T, 8, K, 2>), grid, dim3(256), 0, st, a, a.wgeo); break;
@@ -385,9 +386,10 @@ bool planes4_ok(const Conv2dArgs& a) {
 }
 
 template <typename T, int COUT, int K>
-hipError_t launch_planes_k(hipStream_t st, const Conv2dArgs& a) {
+hipError_t launch_planes_k(hipStream_t st, const Conv2dArgs& a, Conv2dReport* rep) {
   const long long Qtot = (long long)a.B * ((a.Ho + 1) / 2) * a.Wo;
   dim3 grid((unsigned)((Qtot + 255) / 256));
+  if (rep) return report_kernel<T>(rep, "conv2d_planes_kernel", grid, COUT, K, a.ngeo < 4 ? a.ngeo : 4);
   switch (a.ngeo) {
     case 1: hipLaunchKernelGGL((conv2d_planes_kernel<T, COUT, K, 1>), grid, dim3(256), 0, st, a, a.wgeo); break;
     case 2: hipLaunchKernelGGL((conv2d_planes_kernel<T, COUT, K, 2>), grid, dim3(256), 0, st, a, a.wgeo); break;
@@ -409,12 +411,13 @@ bool planes_mfma_ok(const Conv2dArgs& a) {
 }
 
 template <typename T, int K>
-hipError_t launch_planes_mfma_k(hipStream_t st, const Conv2dArgs& a) {
+hipError_t launch_planes_mfma_k(hipStream_t st, const Conv2dArgs& a, Conv2dReport* rep) {
   const int tx = (a.Wo + 63) / 64, ty = (a.Ho + 15) / 16;
   // tiles per block: FeatureNet's RGB conv x20 / GeoFF RGB+depth / depth init at B=4, bf16, 405 / 117 / 73 us at 1
   // tile, 354 / 99 / 62 at 2, 326 / 93 / 59 at 4, 324 / 92 / 59 at 8 (profiles/r06/ab_planes_mfma)
   constexpr int nt = 4;
   const dim3 grid((unsigned)(tx * ((ty + nt - 1) / nt) * a.B));
+  if (rep) return report_kernel<T>(rep, "conv2d_planes_mfma_kernel", grid, K, a.ngeo < 4 ? a.ngeo : 4);
   switch (a.ngeo) {
     case 1: hipLaunchKernelGGL((conv2d_planes_mfma_kernel<T, K, 1>), grid, dim3(256), 0, st, a, tx, ty, nt); break;
     case 2: hipLaunchKernelGGL((conv2d_planes_mfma_kernel<T, K, 2>), grid, dim3(256), 0, st, a, tx, ty, nt); break;
@@ -426,33 +429,34 @@ hipError_t launch_planes_mfma_k(hipStream_t st, const Conv2dArgs& a) {
 
 // Returns hipErrorNotSupported when the layer is not of the fast form (caller uses the MFMA kernel).
 template <typename T>
-hipError_t launch_planes(hipStream_t st, const Conv2dArgs& a) {
+hipError_t launch_planes(hipStream_t st, const Conv2dArgs& a, Conv2dReport* rep) {
   const int K = a.ph[0].ntaps == 9 ? 3 : a.ph[0].ntaps == 25 ? 5 : 0;
   if (K == 0 || a.ngeo < 1 || a.ngeo > 4 || a.cout > 16 || a.cout_pad < 16 || !planes_fast_ok(a, K))
     return hipErrorNotSupported;
-  if (planes_mfma_ok(a)) return K == 3 ? launch_planes_mfma_k<T, 3>(st, a) : launch_planes_mfma_k<T, 5>(st, a);
+  if (planes_mfma_ok(a)) return K == 3 ? launch_planes_mfma_k<T, 3>(st, a, rep) : launch_planes_mfma_k<T, 5>(st, a, rep);
   // 5x5 only: GeoFF stage-3 init convs 5.21-5.28 against 5.30-5.43 ms; at 3x3 (FeatureNet's RGB conv, half of each
   // 12-column window unused, a quarter of the threads) features 2.86-2.89 against 2.77 ms (profiles/r03/ab_planes4.jsonl)
-  if (K == 5 && planes4_ok(a)) return launch_planes4_k<T, 5>(st, a);
-  if (a.cout <= 8) return K == 3 ? launch_planes_k<T, 8, 3>(st, a) : launch_planes_k<T, 8, 5>(st, a);
-  return K == 3 ? launch_planes_k<T, 16, 3>(st, a) : launch_planes_k<T, 16, 5>(st, a);
+  if (K == 5 && planes4_ok(a)) return launch_planes4_k<T, 5>(st, a, rep);
+  if (a.cout <= 8) return K == 3 ? launch_planes_k<T, 8, 3>(st, a, rep) : launch_planes_k<T, 8, 5>(st, a, rep);
+  return K == 3 ? launch_planes_k<T, 16, 3>(st, a, rep) : launch_planes_k<T, 16, 5>(st, a, rep);
 }
 
 // The fast kernels where they take the layer (launch_planes), else the generic one (stride 2, transposed).
 template <typename T>
-hipError_t launch_planes_any(hipStream_t s, const Conv2dArgs& a) {
-  const hipError_t e = launch_planes<T>(s, a);
+hipError_t launch_planes_any(hipStream_t s, const Conv2dArgs& a, Conv2dReport* rep) {
+  const hipError_t e = launch_planes<T>(s, a, rep);
   if (e != hipErrorNotSupported) return e;
   if (a.cout > 16 || a.cout_pad < 16) return hipErrorInvalidValue;
   dim3 grid((unsigned)((a.B * a.Hq * a.Wq + 255) / 256), a.nphase);
+  if (rep) return report_kernel<T>(rep, "conv2d_planes_generic_kernel", grid);
   hipLaunchKernelGGL(conv2d_planes_generic_kernel<T>, grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_conv2d_planes(hipStream_t st, int store, const Conv2dArgs& a) {
-  return store == ST_BF16 ? launch_planes_any<bf16_t>(st, a) : launch_planes_any<float>(st, a);
+hipError_t launch_conv2d_planes(hipStream_t st, int store, const Conv2dArgs& a, Conv2dReport* rep) {
+  return store == ST_BF16 ? launch_planes_any<bf16_t>(st, a, rep) : launch_planes_any<float>(st, a, rep);
 }
 
 }  // namespace damvs

@@ -67,6 +67,14 @@ class HipConv2d:
                                               ctypes.byref(cs)))
         return (B, ho.value, wo.value, cs.value)
 
+    def route(self, B, Hi, Wi, grid=False):
+        """The kernel a call at this size launches under the current switches (damvs_conv2d_route), as tests/isa_pins.json
+        spells it without namespace and parameter list; grid=True: (name, (grid.x, grid.y)). No device work."""
+        buf = ctypes.create_string_buffer(256)
+        check(self._lib.damvs_conv2d_route(self.handle, B, Hi, Wi, buf, len(buf)))
+        name, _, g = buf.value.decode().partition(" grid=")
+        return (name, tuple(int(v) for v in g.strip("()").split(","))) if grid else name
+
     def __call__(self, B, Hi, Wi, in0=None, in1=None, geo=(), res_pre=None, res_post=None, post_up=1, out=None):
         dev = (in0 if in0 is not None else geo[0][0]).device
         shape = self.out_shape(B, Hi, Wi)

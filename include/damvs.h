@@ -262,6 +262,16 @@ int damvs_conv2d_forward(const damvs_conv2d* layer, void* stream, int B, int Hi,
                          const void* in1, const float* const* geo, const long long* geo_batch_stride, const void* res_pre,
                          const void* res_post, int post_up, void* out);
 
+/* ---- introspection ---- */
+/* The kernel damvs_conv2d_forward would launch for this layer at this size under the current
+ * switch settings, as the demangled kernel name without namespace and argument list, e.g.
+ * "conv2d_mfma_kernel<float, 4, true, false, true>", followed by " grid=(x,y)". No device work.
+ * The answer is the forward's for 16-byte aligned planes one image (Hi * Wi floats) apart, as the front-end passes
+ * them: the plane-only layers' vector kernels ask for aligned planes and fall back to the one-column kernel otherwise.
+ * DAMVS_E_ARG: null layer or buffer, or a buffer too small for the answer; DAMVS_E_SHAPE: no kernel takes the layer at
+ * this size (the forward fails too). */
+int damvs_conv2d_route(const damvs_conv2d* layer, int B, int Hi, int Wi, char* buf, size_t n);
+
 /* Border fix-up for a 3x3 padding-1 conv whose bias held the full 9-tap sum of a per-tap constant
  * (a bias that reached the 3x3 conv through a 1x1 conv, FeatureNet's inner2 -> out3,
  * models/module.py:455-459): at every border pixel of out [B][H][W][cout_stored] subtract

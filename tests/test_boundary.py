@@ -54,6 +54,9 @@ def test_arg_errors_without_gpu():
     assert rc == -2
     rc = lib.damvs_stage_create(None, None, 0, 0, ctypes.byref(ctypes.c_void_p()))
     assert rc == -1
+    buf = ctypes.create_string_buffer(64)
+    rc = lib.damvs_conv2d_route(None, 2, 20, 24, buf, len(buf))  # null layer; a null buffer is refused the same way
+    assert rc == -1 and b"null" in lib.damvs_last_error_string()
 
 
 @pytest.mark.parametrize("arch", ["fpn", "unet"])

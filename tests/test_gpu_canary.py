@@ -140,3 +140,92 @@ def test_stage_forward_writes_inside_workspace_and_outputs(case, dtype):
             for k, o in outs.items():
                 o.check(k)
             prob.check("prob_volume")
+
+
+# ---------------------------------------------------------------------------------------------- 2D front-end
+import route_cases  # noqa: E402
+import test_gpu_frontend as FE  # noqa: E402
+from test_gpu_lattice import FPN_SHAPES  # noqa: E402
+
+DT_IDS = {torch.bfloat16: "bf16", torch.float32: "f32"}
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("i", range(len(FE.CASES)))
+def test_conv2d_layers_write_inside_their_outputs(i, dtype):
+    """Every row of test_gpu_frontend.CASES (each 2D kernel family, ragged tiles, channel tails, cout padded to 4) with
+    its output inside guard bands; inputs and residuals are ordinary tensors."""
+    from damvsnet_amd.frontend_hip import planes
+    case = FE.CASES[i]
+    c0, c1, geo, pre, post_up = case[5], case[6], case[7], case[10], case[11]
+    H, W = route_cases.case_size(case)
+    B = route_cases.B
+    L = route_cases.case_layer(case, dtype)
+    shape = L.out_shape(B, H, W)
+    g = torch.Generator(device=DEV).manual_seed(i)
+    rnd = lambda *s: torch.randn(*s, generator=g, device=DEV).to(dtype)  # noqa: E731
+    out = Guarded(shape, dtype)
+    L(B, H, W, rnd(B, H, W, c0) if c0 else None, rnd(B, H, W, c1) if c1 else None,
+      geo=planes(torch.randn(B, len(geo), H, W, generator=g, device=DEV)) if geo else (),
+      res_pre=rnd(*shape) if pre else None,
+      res_post=rnd(B, shape[1] // post_up, shape[2] // post_up, shape[3]) if post_up else None,
+      post_up=max(post_up, 1), out=out.t)
+    out.check("conv2d case %d %s (%s)" % (i, DT_IDS[dtype], L.route(B, H, W)))
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "f32"])
+@pytest.mark.parametrize("Bn,H,W", FPN_SHAPES)
+def test_fpn_top_writes_inside_its_output(Bn, H, W, dtype):
+    """damvs_fpn_top_forward / damvs_fpn_top_forward_f32, then damvs_conv2d_border_bias on the same guarded output."""
+    import torch.nn as nn
+    from damvsnet_amd import _capi
+    from damvsnet_amd.engine import DTYPES
+    from damvsnet_amd.frontend_hip import fpn_top_layers, pack_fpn_top, pack_fpn_top_split
+    g = torch.Generator().manual_seed(H * W)
+    inner2, out3 = nn.Conv2d(8, 32, 1, bias=True), nn.Conv2d(32, 8, 3, padding=1, bias=False)
+    with torch.no_grad():
+        for m in (inner2, out3):
+            m.weight.copy_(torch.randn(m.weight.shape, generator=g) * 0.2)
+    _, _, corr, (wt, wc, bc) = fpn_top_layers(inner2, out3, dtype)
+    c0 = torch.randn(Bn, H, W, 8, generator=g).to(DEV, dtype)
+    f = torch.randn(Bn, H // 2, W // 2, 32, generator=g).to(DEV, dtype)
+    bd = bc.float().to(DEV)
+    lib = _capi.load_library()
+    o = Guarded((Bn, H, W, 8), dtype)
+    st = _capi.stream_ptr(torch.device(DEV))
+    if dtype == torch.bfloat16:
+        ap = pack_fpn_top(wt, wc).to(DEV)
+        _capi.check(lib.damvs_fpn_top_forward(st, Bn, H, W, c0.data_ptr(), f.data_ptr(), ap.data_ptr(), bd.data_ptr(),
+                                              o.t.data_ptr()))
+    else:
+        ap, ws = pack_fpn_top_split(wt, wc)
+        ap = ap.to(DEV)
+        _capi.check(lib.damvs_fpn_top_forward_f32(st, Bn, H, W, c0.data_ptr(), f.data_ptr(), ap.data_ptr(), ws,
+                                                  bd.data_ptr(), o.t.data_ptr()))
+    o.check("fpn top %s" % DT_IDS[dtype])
+    _capi.check(lib.damvs_conv2d_border_bias(st, DTYPES[dtype], Bn, H, W, 8, 8, _capi.float_ptr(corr), o.t.data_ptr()))
+    o.check("fpn top border fix-up %s" % DT_IDS[dtype])
+
+
+@pytest.mark.parametrize("hw", [(37, 51), (8, 9)])
+@pytest.mark.parametrize("masked", [False, True], ids=["basic", "mean"])
+def test_sparse_depth_pyramid_writes_inside_its_outputs(hw, masked):
+    """damvs_sparse_depth_pyramid at odd sizes and at the smallest one: the four levels and the scratch, at exactly the
+    size include/damvs.h asks for, each inside guard bands."""
+    from damvsnet_amd import _capi
+    h, w = hw
+    Bn = 3
+    g = torch.Generator(device=DEV).manual_seed(h * w)
+    depth = 425 + 500 * torch.rand(Bn, h, w, generator=g, device=DEV)
+    depth[:, : h // 3] = 300.0
+    dv = torch.stack([torch.linspace(425, 935, 48), torch.linspace(400, 900, 48), torch.linspace(500, 1000, 48)]).to(DEV)
+    mask = (torch.rand(Bn, h, w, generator=g, device=DEV) > 0.5).float() if masked else None
+    outs = [Guarded((Bn, h >> l, w >> l), torch.float32) for l in range(4)]
+    scratch = Guarded((Bn * (h // 2) * (w // 2) + Bn * (h // 4) * (w // 4),), torch.float32)
+    lib = _capi.load_library()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    _capi.check(lib.damvs_sparse_depth_pyramid(_capi.stream_ptr(torch.device(DEV)), Bn, h, w, p(depth), p(dv), 48,
+                                               p(mask) if masked else None, *[p(o.t) for o in outs], p(scratch.t)))
+    for l, o in enumerate(outs):
+        o.check("sparse pyramid level %d" % l)
+    scratch.check("sparse pyramid scratch")

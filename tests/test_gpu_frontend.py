@@ -32,7 +32,8 @@ def nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
-# (transposed, k, s, p, op, c0, c1, geo positions, cout, relu, pre, post_up)
+# (transposed, k, s, p, op, c0, c1, geo positions, cout, relu, pre, post_up[, (H, W)]); B = 2, 20 x 24 unless given.
+# The comments say what a row is for; the kernel it runs, per dtype and switch setting, is in tests/conv2d_routes.json.
 CASES = [
     (False, 3, 1, 1, 0, 16, 0, (), 32, True, False, 0),
     (False, 5, 2, 2, 0, 8, 0, (), 16, True, False, 0),
@@ -49,14 +50,14 @@ CASES = [
     (False, 3, 1, 1, 0, 256, 0, (), 256, True, False, 0),           # wide layer (cout tiling)
     (False, 3, 1, 1, 0, 32, 32, (64,), 64, True, True, 0),          # two inputs + plane (wide, 64-channel block)
     (True, 5, 2, 2, 1, 128, 0, (), 32, True, False, 1),             # halo kernel: k5 s2 phases, cout 32
-    (True, 3, 1, 1, 0, 64, 0, (), 128, True, True, 0),              # halo kernel: transposed k3 s1, MT 8
+    (True, 3, 1, 1, 0, 64, 0, (), 128, True, True, 0),              # transposed k3 s1, 64 -> 128 (the wide kernel's 128-channel block)
     (True, 4, 2, 1, 0, 16, 0, (), 8, False, False, 0),              # x-pair phases: FPN top (k4 s2), cout 8
     (True, 5, 2, 2, 1, 16, 0, (), 8, True, True, 2),                # x-pair + both residuals (post up 2)
     (True, 3, 2, 1, 1, 16, 16, (), 8, True, False, 1),              # x-pair, two inputs
     (False, 3, 1, 1, 0, 128, 0, (0,), 128, True, True, 0),          # wide kernel: GeoBlock conv2 (plane first)
     (False, 3, 1, 1, 0, 128, 128, (256,), 256, True, True, 2),      # wide: two inputs + plane, both residuals
     (True, 5, 2, 2, 1, 256, 0, (), 128, True, False, 1),            # wide: k5 s2 transposed decoder + skip
-    (False, 1, 1, 0, 0, 64, 0, (64,), 128, False, False, 0),        # wide: 1x1 (GeoBlock downsample)
+    (False, 1, 1, 0, 0, 64, 0, (64,), 128, False, False, 0),        # 1x1 64+g -> 128 (GeoBlock downsample; one tap: the gather kernel)
     (False, 3, 1, 1, 0, 32, 0, (0,), 32, True, True, 0),            # halo, one slice (bf16): 32+g -> 32
     (False, 3, 1, 1, 0, 32, 0, (32,), 16, True, False, 0),          # halo, one slice, one cout tile
     (False, 3, 1, 1, 0, 0, 0, (0, 1, 2), 8, True, False, 0),         # planes: FeatureNet RGB conv 3->8
@@ -68,10 +69,12 @@ CASES = [
     # wide kernel's 64-channel block (4 x 64 q-tiles): GeoBlock 64+g -> 64, transposed k3 s1 128 -> 64
     (False, 3, 1, 1, 0, 64, 0, (64,), 64, True, True, 0, (37, 151)),
     (True, 3, 1, 1, 0, 128, 0, (), 64, True, False, 0, (30, 70)),
-    # 64-channel block at input stride 2 (2 x 64 q-tiles, 32-column waves): GeoBlock conv1 32+32+g -> 64, 32+g -> 64
+    # 64-channel block at input stride 2 (2 x 64 q-tiles, 32-column waves): GeoBlock conv1 32+32+g -> 64 (bf16; fp32 and
+    # the one-input 32+g -> 64, a single 32-channel slice, run on the gather kernel)
     (False, 3, 2, 1, 0, 32, 32, (64,), 64, True, False, 0, (37, 151)),
     (False, 3, 2, 1, 0, 32, 0, (32,), 64, True, True, 0, (64, 130)),
-    # LDS-tiled 3x3 kernel with the GeoBlock depth plane (round 6): cat(g, y) 16+g -> 16, cat(x, g) 16+g -> 32, ragged
+    # LDS-tiled 3x3 kernel with the GeoBlock depth plane (round 6; bf16: fp32 layers with a plane run on the 16-K halo
+    # kernel, 8+g on the 32-K gather kernel): cat(g, y) 16+g -> 16, cat(x, g) 16+g -> 32, ragged
     (False, 3, 1, 1, 0, 16, 0, (0,), 16, True, True, 0, (37, 151)),
     (False, 3, 1, 1, 0, 16, 0, (16,), 32, True, False, 0, (20, 70)),
     (False, 3, 1, 1, 0, 8, 0, (8,), 16, False, False, 2, (22, 64)),
@@ -80,6 +83,46 @@ CASES = [
     (False, 5, 2, 2, 0, 16, 0, (), 32, True, False, 0, (37, 151)),
     (False, 5, 2, 2, 0, 16, 0, (), 16, False, True, 0, (30, 66)),
     (False, 5, 2, 2, 0, 8, 0, (), 32, True, True, 0, (9, 17)),
+    # Rows 41 on: the kernel each one runs is recorded in tests/conv2d_routes.json (HipConv2d.route) and checked on the
+    # GPU by test_conv2d_routes.py, whose coverage test wants every routable conv2d_* instantiation under some row.
+    # Gather kernel with wide cout tiles (gather_mt: ceil(B Hq Wq / 64) nphase MTtot / MT >= 900), smallest B = 2 sizes:
+    (False, 1, 1, 0, 0, 80, 0, (), 128, True, True, 0, (120, 240)),        # bf16 MT 8; f32 MT 4 (K32 and 16-K); partial last K chunk
+    (False, 1, 2, 0, 0, 16, 16, (32,), 56, True, False, 0, (241, 477)),    # two inputs + plane, MT 4 = MTtot, cout 56 of 64, ragged last wave
+    (False, 3, 2, 1, 0, 8, 0, (8,), 24, True, True, 2, (240, 484)),        # MT 2, plane, both residuals, cout 24 of 32
+    (False, 1, 2, 0, 0, 32, 32, (64,), 256, True, False, 0, (200, 288)),   # MTtot 16: bf16 MT 8 grid.y 2, f32 MT 4 grid.y 4
+    (False, 1, 2, 0, 0, 32, 32, (64,), 256, True, False, 0, (200, 162)),   # bf16 MT 4 grid.y 4
+    (False, 1, 2, 0, 0, 32, 32, (64,), 256, True, False, 0, (120, 160)),   # MT 2 grid.y 8
+    (False, 5, 2, 2, 0, 16, 0, (), 64, True, True, 0, (240, 484)),         # MT 4, 25 taps: a tap change inside a K chunk
+    (True, 3, 1, 1, 0, 16, 0, (), 128, True, False, 1, (120, 242)),        # transposed taps, bf16 MT 8, f32 MT 4
+    # rows moved from G32_CASES (DAMVS_CONV2D_G32 does not reroute them: lds_s2, lds_s2, halo 16-K)
+    (False, 5, 2, 2, 0, 8, 0, (), 16, True, False, 0, (60, 84)),
+    (False, 5, 2, 2, 0, 16, 0, (), 32, True, False, 0, (30, 44)),
+    (False, 1, 1, 0, 0, 16, 0, (), 32, False, False, 2, (24, 40)),
+    # halo kernel, two tensor inputs: 32-K (bf16, fp32 split packing) and fp32 16-K; bf16 16+16: the gather kernel TWO, MT 1
+    (False, 3, 1, 1, 0, 32, 32, (), 16, True, False, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 32, 32, (), 32, True, True, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 16, 16, (), 16, True, True, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 16, 16, (), 32, True, False, 2, (22, 38)),
+    # LDS-tiled 3x3: 8 -> 32 (two cout tiles), bf16 32-channel slices without a plane (fp32: halo 32-K)
+    (False, 3, 1, 1, 0, 8, 0, (), 32, True, False, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 32, 0, (), 16, True, True, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 32, 0, (), 32, True, False, 0, (21, 37)),
+    # bf16 wide kernel, 64-channel block at input stride 2, one tensor input (fp32: 32-K gather)
+    (False, 3, 2, 1, 0, 64, 0, (64,), 64, True, False, 0, (21, 70)),
+    # plane-only layers, every plane count: cout 8 (MFMA form; DAMVS_PLANES_MFMA=0: 4-column at 5x5, one-column at 3x3;
+    # DAMVS_PLANES4=0 as well: one-column at 5x5) and cout 12 / 16 (the one-column kernel's 16-channel form)
+    (False, 3, 1, 1, 0, 0, 0, (0,), 8, True, False, 0),
+    (False, 3, 1, 1, 0, 0, 0, (0, 1), 8, True, True, 0),
+    (False, 3, 1, 1, 0, 0, 0, (0, 1, 2, 3), 8, False, False, 2),
+    (False, 5, 1, 2, 0, 0, 0, (0,), 8, True, True, 0),
+    (False, 5, 1, 2, 0, 0, 0, (0, 1, 2), 8, True, False, 0),
+    (False, 3, 1, 1, 0, 0, 0, (0,), 16, True, False, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 0, 0, (0, 1), 12, True, True, 0, (21, 37)),
+    (False, 3, 1, 1, 0, 0, 0, (0, 1, 2, 3), 16, True, False, 2, (22, 38)),
+    (False, 5, 1, 2, 0, 0, 0, (0,), 12, True, False, 0, (21, 37)),
+    (False, 5, 1, 2, 0, 0, 0, (0, 1), 16, True, True, 0, (21, 37)),
+    (False, 5, 1, 2, 0, 0, 0, (0, 1, 2), 16, False, False, 0, (21, 37)),
+    (False, 5, 1, 2, 0, 0, 0, (0, 1, 2, 3), 12, True, False, 0, (21, 37)),
 ]
 
 
@@ -357,7 +400,10 @@ def test_fpn_top_fused_vs_torch(B, H, W, dt, tol):
                                               fd.data_ptr(), fd.data_ptr(), fd.data_ptr(), o.data_ptr()))
 
 
-@pytest.mark.parametrize("k,ng,relu,pre", [(5, 4, True, False), (5, 2, True, True), (5, 1, False, False)])
+PLANES4_CASES = [(5, 4, True, False), (5, 2, True, True), (5, 1, False, False)]
+
+
+@pytest.mark.parametrize("k,ng,relu,pre", PLANES4_CASES)
 def test_planes_four_columns_bitwise(k, ng, relu, pre, monkeypatch):
     """The 4-column plane-only kernel (conv2d_planes4_kernel: FeatureNet's RGB conv, GeoFF's RGB+depth and depth init
     convs) against the one-column kernel it replaces: same fused multiply-adds per output, so bitwise equal (odd H,
@@ -373,6 +419,9 @@ def test_planes_four_columns_bitwise(k, ng, relu, pre, monkeypatch):
     res = torch.randn(B, H, W, cout, generator=g).to(DEV, torch.bfloat16) if pre else None
     L = HipConv2d(conv, torch.bfloat16, relu, geo_at=tuple(range(ng)), c0=0, c1=0, c1_at=0)
     monkeypatch.setenv("DAMVS_PLANES_MFMA", "0")  # the VALU kernels (the MFMA form takes these layers by default)
+    from route_cases import flips
+    flips(L, B, H, W, monkeypatch, "DAMVS_PLANES4", "conv2d_planes4_kernel<unsigned short, 8, %d, %d>" % (k, ng),
+          "conv2d_planes_kernel<unsigned short, 8, %d, %d>" % (k, ng))
     outs = []
     for flag in ("1", "0"):
         monkeypatch.setenv("DAMVS_PLANES4", flag)
@@ -383,7 +432,8 @@ def test_planes_four_columns_bitwise(k, ng, relu, pre, monkeypatch):
 
 # The LDS-tiled 3x3 kernel with a depth plane (conv2d_lds_kernel, round 6) against the gather kernel it replaces
 # (DAMVS_CONV2D_LDS_PLANE=0): the same MFMA sequence per accumulator (tensor chunks, then the plane chunk), so bitwise
-# equal in bf16 (fp32: the gather kernel is the 32-K form, compared against torch in test_conv2d_layer_vs_torch).
+# equal in bf16 (fp32 layers with a plane never run on the LDS kernel: lds3_route leaves them to the halo or 32-K gather
+# kernel, compared against torch in test_conv2d_layer_vs_torch).
 LDS_PLANE_CASES = [
     (16, (0,), 16, True, True, 0, (37, 151)),   # GeoBlock conv2: cat(g2, y) 16+g -> 16, identity residual
     (16, (16,), 32, True, False, 0, (20, 70)),  # GeoBlock conv1 at stride 1: cat(x, g1) 16+g -> 32
@@ -409,6 +459,9 @@ def test_lds_plane_bitwise_vs_gather(case, monkeypatch):
     res = torch.randn(B, H, W, L.cout_store, generator=g).to(DEV, dt) if pre else None
     post = torch.randn(B, H // max(post_up, 1), W // max(post_up, 1), L.cout_store, generator=g).to(DEV, dt) \
         if post_up else None
+    from route_cases import flips
+    flips(L, B, H, W, monkeypatch, "DAMVS_CONV2D_LDS_PLANE", "conv2d_lds_kernel<unsigned short, %d, %d>" % (c0, (cout + 15) // 16),
+          "conv2d_mfma_kernel<unsigned short, 1, false, false, false>")
     outs = []
     for flag in ("1", "0"):
         monkeypatch.setenv("DAMVS_CONV2D_LDS_PLANE", flag)
@@ -444,6 +497,10 @@ def test_xpair_lds_bitwise_vs_gather(case, dt, monkeypatch):
     res = torch.randn(B, Ho, Wo, L.cout_store, generator=g).to(DEV, dt) if pre else None
     post = torch.randn(B, Ho // max(post_up, 1), Wo // max(post_up, 1), L.cout_store, generator=g).to(DEV, dt) \
         if post_up else None
+    from route_cases import flips
+    T = "float" if dt == torch.float32 else "unsigned short"
+    flips(L, B, H, W, monkeypatch, "DAMVS_CONV2D_XPAIR_LDS", "conv2d_xpair_lds_kernel<%s>" % T,
+          "conv2d_mfma_kernel<%s, 1, false, true, false>" % T)
     outs = []
     for flag in ("1", "0"):
         monkeypatch.setenv("DAMVS_CONV2D_XPAIR_LDS", flag)
@@ -494,6 +551,10 @@ def test_planes_mfma_vs_fp64_and_valu(case, dtype, monkeypatch):
     L = HipConv2d(conv, dtype, relu, geo_at=tuple(range(ng)), c0=0, c1=0, c1_at=0)
     run = lambda: L(B, H, W, None, None, geo=gp, res_pre=res.to(DEV, dtype) if res is not None else None,
                     res_post=post.to(DEV, dtype) if post is not None else None, post_up=max(post_up, 1)).clone()
+    from route_cases import flips
+    T = "float" if dtype == torch.float32 else "unsigned short"
+    flips(L, B, H, W, monkeypatch, "DAMVS_PLANES_MFMA", "conv2d_planes_mfma_kernel<%s, %d, %d>" % (T, k, ng),
+          "conv2d_planes%s_kernel<%s, 8, %d, %d>" % ("4" if k == 5 else "", T, k, ng))  # VALU: 4-column at 5x5
     got = run()
     monkeypatch.setenv("DAMVS_PLANES_MFMA", "0")
     valu = run()
@@ -544,6 +605,9 @@ def test_wide_rolling_loop_bitwise(case, monkeypatch):
     rp = torch.randn(B, Ho, Wo, L.cout_store, generator=g).to(DEV) if pre else None
     rq = torch.randn(B, Ho // post_up, Wo // post_up, L.cout_store, generator=g).to(DEV) if post_up else None
     run = lambda: L(B, H, W, a, b, geo=gp, res_pre=rp, res_post=rq, post_up=max(post_up, 1))  # noqa: E731
+    from route_cases import flips
+    flips(L, B, H, W, monkeypatch, "DAMVS_WIDE_RS", "conv2d_wide_kernel<float, %s, 1, 2, true, false>" % ("true" if c1 else "false"),
+          "conv2d_wide_kernel<float, %s, 1, 2, false, false>" % ("true" if c1 else "false"))
     monkeypatch.delenv("DAMVS_WIDE_RS", raising=False)
     y_rs = run()
     monkeypatch.setenv("DAMVS_WIDE_RS", "0")
@@ -584,6 +648,9 @@ def test_wide_s2_one_row_tiles_bitwise(case, monkeypatch):
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     rp = torch.randn(B, Ho, Wo, L.cout_store, generator=g).to(DEV) if pre else None
     run = lambda: L(B, H, W, a, b, geo=gp, res_pre=rp)  # noqa: E731
+    from route_cases import flips
+    flips(L, B, H, W, monkeypatch, "DAMVS_WIDE_S2R1", "conv2d_wide_kernel<float, %s, 2, 2, false, true>" % ("true" if c1 else "false"),
+          "conv2d_wide_kernel<float, %s, 2, 2, false, false>" % ("true" if c1 else "false"))
     monkeypatch.setenv("DAMVS_WIDE_S2R1", "0")
     y2 = run()
     monkeypatch.delenv("DAMVS_WIDE_S2R1")  # default: one-row tiles
@@ -597,12 +664,15 @@ def test_wide_s2_one_row_tiles_bitwise(case, monkeypatch):
 # MFMAs) against the 16-K form (DAMVS_CONV2D_G32=0): the same products summed in another order, so equal to fp32
 # rounding. FeatureNet's k5 s2 convs, the 1x1 GeoBlock downsamples (two inputs + plane, stride 2), the FPN inner conv
 # with the upsampled residual, GeoFF's full-resolution stride-2 conv with the depth plane.
+# (The fp32 5x5 s2 layers of 8 / 16 channels run on conv2d_lds_s2_kernel and 1x1 16 -> 32 on the 16-K halo kernel whatever
+# the switch says: those three rows are rows 49-51 of CASES now, and rows 0, 1 and 4 here are gather layers with cout tiles
+# of 4: 1x1 80 -> 128 with a partial last K chunk, 1x1 s2 two inputs + plane, 5x5 s2 16 -> 64.)
 G32_CASES = [
-    (False, 5, 2, 2, 0, 8, 0, (), 16, True, False, 0, (60, 84)),
-    (False, 5, 2, 2, 0, 16, 0, (), 32, True, False, 0, (30, 44)),
+    (False, 1, 1, 0, 0, 80, 0, (), 128, True, False, 0, (120, 240)),
+    (False, 1, 2, 0, 0, 16, 16, (32,), 56, True, False, 0, (241, 477)),
     (False, 1, 2, 0, 0, 128, 128, (256,), 256, True, False, 0, (20, 26)),
     (False, 1, 1, 0, 0, 64, 0, (64,), 128, True, False, 0, (19, 30)),
-    (False, 1, 1, 0, 0, 16, 0, (), 32, False, False, 2, (24, 40)),
+    (False, 5, 2, 2, 0, 16, 0, (), 64, True, False, 2, (240, 484)),
     (False, 3, 2, 1, 0, 8, 0, (8,), 16, True, False, 0, (40, 72)),
 ]
 
@@ -629,6 +699,10 @@ def test_gather_conv2d_k32_vs_k16_fp32(case, monkeypatch):
     Ho, Wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
     rq = torch.randn(B, Ho // post_up, Wo // post_up, L.cout_store, generator=g).to(DEV) if post_up else None
     run = lambda: L(B, H, W, a, b, geo=gp, res_post=rq, post_up=max(post_up, 1))  # noqa: E731
+    from route_cases import flips
+    k32, k16 = flips(L, B, H, W, monkeypatch, "DAMVS_CONV2D_G32", r"conv2d_mfma_kernel<float, [124], (true|false), false, true>",
+                     r"conv2d_mfma_kernel<float, [124], (true|false), false, false>")
+    assert k32[:-len("true>")] == k16[:-len("false>")], (k32, k16)  # the same cout tile and input count
     monkeypatch.delenv("DAMVS_CONV2D_G32", raising=False)
     y32 = run()
     monkeypatch.setenv("DAMVS_CONV2D_G32", "0")
@@ -675,6 +749,9 @@ def test_halo_rolling_loop_bitwise(case, monkeypatch):
     rp = torch.randn(B, Ho, Wo, L.cout_store, generator=g).to(DEV) if pre else None
     rq = torch.randn(B, Ho // post_up, Wo // post_up, L.cout_store, generator=g).to(DEV) if post_up else None
     run = lambda: L(B, H, W, a, b, geo=gp, res_pre=rp, res_post=rq, post_up=max(post_up, 1))  # noqa: E731
+    from route_cases import flips
+    form = "conv2d_halo_kernel<float, %d, 1, %s, true, %%s>" % ((cout + 15) // 16, "true" if c1 else "false")
+    flips(L, B, H, W, monkeypatch, "DAMVS_HALO_RS", form % "true", form % "false")
     monkeypatch.delenv("DAMVS_HALO_RS", raising=False)
     y_rs = run()
     monkeypatch.setenv("DAMVS_HALO_RS", "0")

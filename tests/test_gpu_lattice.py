@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import route_cases
 from conftest import rel_max
 from test_gpu_frontend import CASES as CONV2D_CASES
 
@@ -372,6 +373,23 @@ def test_one_dropped_tap_passes_rel_max_but_not_equality():
     assert rel_max(a.float().numpy(), b.float().numpy()) < 2e-2
 
 
+def test_shifted_cout_block_fails_equality():
+    """What the wide-cout-tile rows are for: block row blockIdx.y of the gather kernel stores cout tiles mt0 + m, mt0 = MT
+    * blockIdx.y. Take the 64+g -> 256 row's reference (bf16: MT 8, two block rows, the second owns channels 128..255)
+    with the second block row's tiles shifted by one 16-channel tile, as an mt0 slip would store them (the last tile
+    then holds what lies past cout: nothing). It differs from the true reference by at least 0.5 on more than 25 % of
+    all elements, so the equality gate sees it."""
+    i = next(n for n, c in enumerate(CONV2D_CASES)
+             if c[:12] == (False, 1, 2, 0, 0, 32, 32, (64,), 256, True, False, 0) and c[12] == (200, 288))
+    fx = conv2d_fixture(i)
+    wrong = fx.ref.clone()
+    wrong[:, 128:240] = fx.ref[:, 144:256]
+    wrong[:, 240:] = 0
+    assert not torch.equal(wrong.to(BF16), fx.ref.to(BF16))
+    off = float(((wrong - fx.ref).abs() >= 0.5).double().mean())
+    assert off > 0.25, off
+
+
 # ---------------------------------------------------------------------------------------------- the GPU tests
 
 DT_IDS = {BF16: "bf16", F32: "f32"}
@@ -384,6 +402,22 @@ def test_conv2d_layer_exact(i, dtype, _lib):
     """Every form of test_gpu_frontend.CASES on lattice data: equal to the float64 reference on the first cout channels,
     exactly 0 on the padded channels up to cout_store."""
     run_conv2d_layer(conv2d_fixture(i), dtype, "conv2d case %d %s" % (i, DT_IDS[dtype]))
+
+
+# The rows that a switch routes to another kernel, with that switch off: every "cases" entry of tests/conv2d_routes.json
+# beyond the defaults (tests/route_cases.py). The kernels behind the A/B switches (the VALU plane kernels in bf16, the
+# 16-K gather form, the wide and halo kernels' plain loops, the x-pair gather form) meet the reference themselves here.
+SWITCHED_RUNS = route_cases.exact_runs(switched_only=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("i,dt,off", SWITCHED_RUNS, ids=[route_cases.case_key(*r) for r in SWITCHED_RUNS])
+def test_conv2d_layer_exact_switched(i, dt, off, _lib, monkeypatch):
+    for sw in off:
+        monkeypatch.setenv(sw, "0")
+    key = route_cases.case_key(i, dt, off)
+    assert route_cases.case_route(i, dt) == route_cases.load()["cases"][key], key   # the switched kernel, not the default once more
+    run_conv2d_layer(conv2d_fixture(i), route_cases.DTYPES[dt], "conv2d case %s" % key)
 
 
 def run_conv2d_layer(fx, dtype, what, equal=assert_lattice_equal):

@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import route_cases
 import test_gpu_lattice as L
 from conftest import rel_max
 from test_gpu_lattice import (B, CONV2D_CASES, FPN_SHAPES, SWITCH_SHAPE, UNET_C, UNET_SHAPES, _lib,  # noqa: F401
@@ -172,7 +173,8 @@ def split_equal(fx):
 # Cases whose default draw misses a condition of check_two_piece get another activation density or seed here (never another
 # condition). Three planes have one odd channel: at activation density 0.5 only 1/6 of the elements would carry a lo
 # piece. Two planes and two output channels leave two two-piece weights per tap: the seed is one whose draw covers all.
-CONV2D_DRAWS = {6: dict(act_density=0.75), 25: dict(act_density=0.75), 7: dict(seed=7003)}
+CONV2D_DRAWS = {6: dict(act_density=0.75), 25: dict(act_density=0.75), 7: dict(seed=7003), 64: dict(act_density=0.75),
+                70: dict(act_density=0.75)}
 
 
 @functools.lru_cache(maxsize=2)
@@ -194,14 +196,21 @@ def is_xpair(case):
     return tr and s == 2 and cout == 8 and not geo          # weight_pack.h pack_conv2d
 
 
-# The rows DAMVS_CONV2D_G32=0 can reroute are those with a 32-K split packing (weight_pack.h pack_conv2d) that
-# conv2d_route leaves to the gather kernel; the packing's condition alone is stated here, so a row that the wide, halo or
-# LDS kernels take runs its usual kernel once more. DAMVS_PLANES_MFMA=0 reroutes the plane-only rows.
-G32_ROWS = [i for i, c in enumerate(CONV2D_CASES)
+# A layer with one input channel (the one-plane rows) has no odd channel to carry a two-piece activation: those rows run
+# on the lattice alone (test_gpu_lattice.py).
+SPLIT_ROWS = [i for i, c in enumerate(CONV2D_CASES) if c[5] + c[6] + len(c[7]) >= 2]
+# The switched runs are the fp32 entries of tests/conv2d_routes.json beyond the defaults: the rows a switch routes to
+# another kernel, with that switch off (the 16-K gather form, the VALU plane kernels, the wide and halo kernels' plain
+# loops, the x-pair gather form). The test asserts the recorded kernel before it runs. Rows 0-40 also keep the runs they
+# had before the table existed, picked by the packing's condition alone (G32_ROWS) or for being plane-only (PLANE_ROWS):
+# where the table has no entry for such a run the switch leaves the row on its usual kernel, which the test asserts too.
+G32_ROWS = [i for i, c in enumerate(CONV2D_CASES[:41])
             if not is_xpair(c) and c[5] % 8 == 0 and c[6] % 8 == 0 and c[5] + c[6] >= 8 and len(c[7]) <= 1]
-PLANE_ROWS = [i for i, c in enumerate(CONV2D_CASES) if c[5] + c[6] == 0]
-CONV2D_RUNS = ([(i, None) for i in range(len(CONV2D_CASES))] + [(i, "DAMVS_CONV2D_G32") for i in G32_ROWS] +
-               [(i, "DAMVS_PLANES_MFMA") for i in PLANE_ROWS])
+PLANE_ROWS = [i for i, c in enumerate(CONV2D_CASES[:41]) if c[5] + c[6] == 0]
+ROUTES = route_cases.load()["cases"]
+CONV2D_RUNS = ([(i, ()) for i in SPLIT_ROWS] +
+               sorted({(i, off) for i, _, off in route_cases.exact_runs(("f32",), switched_only=True) if i in SPLIT_ROWS} |
+                      {(i, ("DAMVS_CONV2D_G32",)) for i in G32_ROWS} | {(i, ("DAMVS_PLANES_MFMA",)) for i in PLANE_ROWS}))
 
 
 # ---------------------------------------------------------------------------------------------- fused FPN top
@@ -278,7 +287,7 @@ def test_two_piece_fixtures_are_exact(group):
     split_exponent; U-Net activations times each batch element's prescale). The FPN top's packed weight halves are
     those of the lattice fixture (lo = 0). The zero-shift net folds to the lattice scales and a shift of exactly 0."""
     if group == "conv2d":
-        for i in range(len(CONV2D_CASES)):
+        for i in SPLIT_ROWS:
             check_two_piece("conv2d case %d" % i, conv2d_split_fixture(i))
     elif group == "fpn_top":
         from damvsnet_amd.frontend_hip import _fpn_top_A, pack_fpn_top_split
@@ -351,18 +360,22 @@ def test_one_dropped_lo_tap_passes_rel_max_but_not_equality():
 # ---------------------------------------------------------------------------------------------- the GPU tests
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("i,switch", CONV2D_RUNS,
-                         ids=["%d%s" % (i, "-%s=0" % sw[6:] if sw else "") for i, sw in CONV2D_RUNS])
-def test_conv2d_layer_split_exact(i, switch, _lib, monkeypatch):  # noqa: F811
+@pytest.mark.parametrize("i,off", CONV2D_RUNS,
+                         ids=["%d%s" % (i, "".join("-%s=0" % sw[6:] for sw in off)) for i, off in CONV2D_RUNS])
+def test_conv2d_layer_split_exact(i, off, _lib, monkeypatch):  # noqa: F811
     """Every form of test_gpu_frontend.CASES in fp32 on two-piece data, driven as test_conv2d_layer_exact drives it:
     equal to the float64 reference on the first cout channels, exactly 0 on the padded ones. Case 0 (16 -> 32, 3x3) is
     the smallest and runs first: it is also the check that the matrix core keeps an exact fp32 sum over the 23 bits
     these fixtures span. With DAMVS_CONV2D_G32=0 / DAMVS_PLANES_MFMA=0 the 16-K gather form and the VALU plane
     kernels meet the reference themselves (their sibling tests are tolerance tests)."""
     fx = conv2d_split_fixture(i)
-    if switch:
-        monkeypatch.setenv(switch, "0")
-    L.run_conv2d_layer(fx, F32, "conv2d case %d f32 two-piece %s" % (i, switch or ""), split_equal(fx))
+    for sw in off:
+        monkeypatch.setenv(sw, "0")
+    default, key = ROUTES[route_cases.case_key(i, "f32")], route_cases.case_key(i, "f32", off)
+    want = ROUTES.get(key, default)   # no entry: the switch does not reroute this row
+    assert route_cases.case_route(i, "f32") == want, key
+    assert key not in ROUTES or not off or want != default, key
+    L.run_conv2d_layer(fx, F32, "conv2d case %s two-piece" % key, split_equal(fx))
 
 
 @pytest.mark.gpu
