@@ -4,7 +4,7 @@ Heavy imports (torch modules, the HIP library) are lazy so that ``damvsnet_amd.s
 ``damvsnet_amd.weights`` stay importable without a GPU or a built library.
 """
 
-__all__ = ["CascadeMVSNet", "DepthNet", "homo_warping", "load_library"]
+__all__ = ["CascadeMVSNet", "DepthNet", "homo_warping", "load_library", "SceneMaps", "reconstruct_scene"]
 
 
 def __getattr__(name):
@@ -14,6 +14,9 @@ def __getattr__(name):
     if name in ("DepthNet", "homo_warping"):
         from . import depthnet
         return getattr(depthnet, name)
+    if name in ("SceneMaps", "reconstruct_scene"):
+        from . import scene
+        return getattr(scene, name)
     if name == "load_library":
         from ._capi import load_library
         return load_library

@@ -46,6 +46,7 @@ class DamvsConv2dDesc(ctypes.Structure):
 
 
 FUSION_MAX_SRC = 10
+SCENE_MAX_BATCH = 64
 _f = ctypes.c_float
 
 
@@ -119,6 +120,8 @@ SIGNATURES = (
     ("damvs_fusion_cloud_scratch", c_int, (c_int, c_int)),
     ("damvs_fusion_cloud", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
                                    c_void_p, ctypes.c_longlong, c_void_p)),
+    ("damvs_scene_ingest", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, ctypes.c_longlong, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p)),
     ("damvs_conv2d_border_bias", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                          ctypes.POINTER(ctypes.c_float), c_void_p)),
 )

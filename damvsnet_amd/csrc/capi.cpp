@@ -291,13 +291,14 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #ifndef DAMVS_BUILD_ID
 #define DAMVS_BUILD_ID "unstamped"
 #endif
-// The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so) carry the same
+// The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so) carry the same
 // one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
   static const std::string id = [] {
     std::string s(DAMVS_BUILD_ID);
     const std::pair<const char*, const char*> side[] = {{"libdamvs_fusion.so", fusion_static_build_id()},
-                                                        {"libdamvs_cloud.so", fusion_cloud_build_id()}};
+                                                        {"libdamvs_cloud.so", fusion_cloud_build_id()},
+                                                        {"libdamvs_scene.so", scene_build_id()}};
     for (const auto& l : side)
       if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
     return s;
@@ -971,6 +972,48 @@ int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, co
   a.capacity = capacity;
   a.cursor = cursor;
   return hip_check(launch_fusion_cloud(static_cast<hipStream_t>(stream), a), "fusion_cloud launch");
+}
+
+// ============================================================================ scene ingest
+int damvs_scene_ingest(void* stream, int B, int H, int W, int V, const float* depth, const float* conf3,
+                       const float* conf2, const float* conf1, const float* img, long long img_batch_stride,
+                       const int* slots, float* depth_store, float* conf_store, unsigned char* rgb_store) {
+  if (!depth || !conf3 || !conf2 || !conf1 || !slots || !depth_store || !conf_store)
+    return fail(DAMVS_E_ARG, "null argument");
+  if (img && !rgb_store) return fail(DAMVS_E_ARG, "null rgb_store with an image to convert");
+  if (B < 1 || B > kSceneMaxBatch) return fail(DAMVS_E_SHAPE, "B %d not in [1, %d]", B, kSceneMaxBatch);
+  if (H < 4 || W < 4 || H % 4 || W % 4)
+    return fail(DAMVS_E_SHAPE, "H and W must be positive multiples of 4 (got %d x %d)", H, W);
+  if (V < 1) return fail(DAMVS_E_SHAPE, "V %d < 1", V);
+  if ((long long)H * W * 12 >= (1LL << 31))
+    return fail(DAMVS_E_SHAPE, "%d x %d: a view's confidence and colour planes must be smaller than 2 GiB", H, W);
+  SceneArgs a;
+  for (int b = 0; b < B; ++b) {
+    if (slots[b] < 0 || slots[b] >= V) return fail(DAMVS_E_ARG, "slot %d of sample %d outside [0, %d)", slots[b], b, V);
+    for (int c = 0; c < b; ++c)
+      if (slots[c] == slots[b]) return fail(DAMVS_E_ARG, "slot %d repeated (samples %d and %d)", slots[b], c, b);
+    a.slots[b] = slots[b];
+  }
+  for (int b = B; b < kSceneMaxBatch; ++b) a.slots[b] = 0;
+  // the kernel moves 4 pixels per 16-byte access (the stage-2 pair per 8-byte load)
+  auto misaligned = [](const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) != 0; };
+  if (misaligned(depth, 16) || misaligned(conf3, 16) || misaligned(conf2, 8) || misaligned(conf1, 4) ||
+      misaligned(depth_store, 16) || misaligned(conf_store, 16) || misaligned(rgb_store, 4))
+    return fail(DAMVS_E_ARG, "misaligned map (16 bytes for the full-size maps and stores, 8 for conf2, 4 for rgb_store)");
+  if (img && (misaligned(img, 16) || img_batch_stride % 4))
+    return fail(DAMVS_E_ARG, "img must be 16-byte aligned with a batch stride that is a multiple of 4 floats");
+  a.H = H;
+  a.W = W;
+  a.depth = depth;
+  a.conf3 = conf3;
+  a.conf2 = conf2;
+  a.conf1 = conf1;
+  a.img = img;
+  a.img_bstride = img_batch_stride;
+  a.depth_store = depth_store;
+  a.conf_store = conf_store;
+  a.rgb_store = img ? rgb_store : nullptr;
+  return hip_check(launch_scene_ingest(static_cast<hipStream_t>(stream), B, a), "scene_ingest launch");
 }
 
 }  // extern "C"

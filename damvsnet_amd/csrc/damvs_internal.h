@@ -206,6 +206,25 @@ int fusion_cloud_tiles(long long n);
 hipError_t launch_fusion_cloud(hipStream_t s, const CloudArgs& a);
 const char* fusion_cloud_build_id();
 
+// ---------------------------------------------------------------- scene ingest (k_scene.hip, libdamvs_scene.so)
+constexpr int kSceneMaxBatch = 64;                  // DAMVS_SCENE_MAX_BATCH: the slot table lives in the kernel arguments
+constexpr int kSceneBlockX = 64, kSceneBlockY = 4;  // threads: 64 groups of 4 pixels across, 4 rows
+struct SceneArgs {
+  int H, W;                   // multiples of 4, H * W * 12 < 2^31
+  const float* depth;         // [B][H][W]
+  const float* conf3;         // [B][H][W]
+  const float* conf2;         // [B][H/2][W/2]
+  const float* conf1;         // [B][H/4][W/4]
+  const float* img;           // sample b: img + b * img_bstride, three planes [H][W]; nullptr: rgb not written
+  long long img_bstride;      // floats
+  float* depth_store;         // [V][H][W]
+  float* conf_store;          // [V][3][H][W]: final, stage 2, stage 1
+  unsigned char* rgb_store;   // [V][H][W][3]
+  int slots[kSceneMaxBatch];  // sample b -> slot
+};
+hipError_t launch_scene_ingest(hipStream_t s, int B, const SceneArgs& a);
+const char* scene_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -200,6 +200,20 @@ def fuse_scene(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0.1
                 raise ValueError("image of view %d: %s %s, expected uint8 %s" % (
                     ref_view, img.dtype, img.shape, tuple(depths[ref_view].shape) + (3,)))
             rgbs[ref_view] = up(img)
+    return fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf, dist_base, rel_diff_base, method,
+                         thres_view, os.path.join(out_folder, "mask") if save_masks else None, max_points, device)
+
+
+def fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25,
+                  rel_diff_base=1 / 1300, method="dypcd", thres_view=5, mask_dir=None, max_points=None, device="cuda"):
+    """The per-pair loop of fuse_scene and scene.SceneMaps.fuse over maps already on the device: dicts by view id of
+    cams (K, E) host arrays, depths (H, W) float32, and for the reference views confs (final, stage 2, stage 1) and rgbs
+    (H, W, 3) uint8. Per pair the fusion kernel and compact_cloud on one cursor, no host synchronisation between views;
+    then the mask PNGs (mask_dir, None: not written), one copy of count * 15 bytes and mvsio.write_ply_records.
+    Raises ValueError, writing no PLY, when the cloud does not fit max_points. Returns the point count."""
+    if method not in METHODS:
+        raise ValueError("fusion method %r not in %s" % (method, METHODS))
+    save_masks = mask_dir is not None
     capacity = sum(depths[r].numel() for r, _ in pairs)
     if max_points is not None:
         capacity = max(0, min(capacity, int(max_points)))
@@ -216,11 +230,11 @@ def fuse_scene(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0.1
         if save_masks:
             masks.append((ref_view, mask))
     if save_masks:
-        os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+        os.makedirs(mask_dir, exist_ok=True)
         for ref_view, mask in masks:
             m = mask.cpu().numpy()
             for bit, kind in ((1, "photo"), (2, "geo"), (4, "final")):
-                _save_mask(os.path.join(out_folder, "mask", "%08d_%s.png" % (ref_view, kind)), (m & bit) != 0)
+                _save_mask(os.path.join(mask_dir, "%08d_%s.png" % (ref_view, kind)), (m & bit) != 0)
     count = int(cursor.item())
     if count > capacity:
         raise ValueError("the scene's point cloud needs %d points, the record buffer holds %d" % (count, capacity))

@@ -195,10 +195,15 @@ class EvalScenes:
     """The reference's eval dataset (datasets/general_eval.py:8-199) over a DTU-style tree
     <datapath>/<scan>/{pair.txt, cams/%08d_cam.txt, images[_post]/%08d.jpg}: item i is the sample
     dict CascadeMVSNet.forward consumes (imgs (N,3,H,W), proj_matrices per stage, depth_values,
-    intrinsics_matrices per stage, filename pattern)."""
+    intrinsics_matrices per stage, filename pattern).
+    ``cache_views`` (off by default, as the reference): keep each view's decoded image and camera after
+    scale_mvs_input, keyed by (scan, view id), so a view listed by several samples (five at nviews 5) is read and
+    resized once; the samples are the same arrays either way. The cache lives as long as the dataset: one scene's
+    images at the working size (23 MB each at 1184 x 1600)."""
 
     def __init__(self, datapath, scans, nviews, ndepths=192, interval_scale=1.06, max_h=1184, max_w=1600,
-                 fix_res=False):
+                 fix_res=False, cache_views=False):
+        self._views = {} if cache_views else None
         self.datapath, self.nviews, self.ndepths = datapath, nviews, ndepths
         self.max_h, self.max_w = max_h, max_w
         self.fix_res, self.fix_wh, self._s = fix_res, False, None
@@ -219,10 +224,17 @@ class EvalScenes:
         view_ids = [ref_view] + src_views[:self.nviews - 1]
         imgs, projs, depth_values, K = [], [], None, None
         for i, vid in enumerate(view_ids):
-            img = read_img(self._img_path(scan, vid))
-            K, E, dmin, dint = read_cam_file(os.path.join(self.datapath, scan, "cams", "%08d_cam.txt" % vid),
-                                             self.ndepths, self.interval_scale[scan])
-            img, K = scale_mvs_input(img, K, self.max_w, self.max_h)
+            hit = self._views.get((scan, vid)) if self._views is not None else None
+            if hit is None:
+                img = read_img(self._img_path(scan, vid))
+                K, E, dmin, dint = read_cam_file(os.path.join(self.datapath, scan, "cams", "%08d_cam.txt" % vid),
+                                                 self.ndepths, self.interval_scale[scan])
+                img, K = scale_mvs_input(img, K, self.max_w, self.max_h)
+                if self._views is not None:
+                    self._views[(scan, vid)] = (img, K.copy(), E, dmin, dint)
+            else:
+                img, K, E, dmin, dint = hit
+                K = K.copy()  # scaled in place below
             if self.fix_res:  # one standard size for the whole scene (general_eval.py:133-137)
                 self._s = img.shape[:2]
                 self.fix_res, self.fix_wh = False, True

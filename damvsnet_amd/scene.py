@@ -1,0 +1,219 @@
+"""Scene reconstruction in memory: a forward's outputs go to depth fusion while they
+are still on the device, and one call leads from a scene directory to a PLY.
+
+The reference's test path (test_uni.py:246-287) copies six maps per reference view to the host, writes them as PFMs with
+the camera and the image, and its filter (filter/dypcd.py:198-209) reads four of them back per view. Here
+`SceneMaps.add` hands a batch of `CascadeMVSNet.forward` outputs to one HIP launch (k_scene.hip, damvs_scene_ingest)
+that writes each sample into its slot of three scene-resident stores: the final depth, the three confidences at the
+final resolution (stage 1 and 2 upsampled by nearest neighbour, mvsio.resize_nearest at exactly x4 / x2) and the
+reference image as uint8 HWC. `SceneMaps.fuse` runs fusion.fuse_scene's per-pair loop over those stores
+(fusion.fuse_resident), `SceneMaps.save` writes the reference's tree for tools that want the files, and
+`reconstruct_scene` drives the whole path for one scan.
+
+A stated difference: the reference re-encodes the reference image as JPEG (test_uni.py:286-287) and the fusion reads
+that file back, so its colours carry JPEG loss. The in-memory path takes the colour before the JPEG. Positions, masks
+and point order are those of the file path bit for bit; colours are equal whenever the file path's images are lossless.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _capi, fusion, mvsio
+from ._capi import check
+
+
+class SceneMaps:
+    """The scene-resident inputs of depth fusion for the listed views, all of one size (H, W multiples of 4):
+    `depth` (V, H, W) float32, `conf` (V, 3, H, W) float32 in the order the fusion kernels take them (final, stage 2,
+    stage 1) and `rgb` (V, H, W, 3) uint8 on `device`, view i of `view_ids` in slot i, and on the host `cams`, a dict
+    view id -> (K (3, 3), E (4, 4)) float32. A slot holds nothing until its view is added."""
+
+    def __init__(self, view_ids, H, W, device="cuda"):
+        view_ids = [int(v) for v in view_ids]
+        if len(set(view_ids)) != len(view_ids) or not view_ids:
+            raise ValueError("view_ids must be a non-empty list of distinct view ids")
+        if H < 4 or W < 4 or H % 4 or W % 4:
+            raise ValueError("H and W must be positive multiples of 4 (got %d x %d)" % (H, W))
+        self.view_ids, self.H, self.W, self.device = view_ids, int(H), int(W), torch.device(device)
+        self.slot = {v: i for i, v in enumerate(view_ids)}
+        V = len(view_ids)
+        self.depth = torch.empty(V, H, W, device=self.device, dtype=torch.float32)
+        self.conf = torch.empty(V, 3, H, W, device=self.device, dtype=torch.float32)
+        self.rgb = torch.empty(V, H, W, 3, device=self.device, dtype=torch.uint8)
+        self.cams = {}
+        self._cam_files = {}  # view id -> the (2, 4, 4) array mvsio.write_cam takes
+        self._added, self._coloured = set(), set()
+
+    # ------------------------------------------------------------------------------------------------- add
+    def _check_map(self, t, name, shape, views):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != self.depth.device:
+            raise ValueError("%s of views %s must be a CUDA tensor on %s" % (name, views, self.depth.device))
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("%s of views %s must be contiguous float32 (got %s%s)" % (
+                name, views, t.dtype, "" if t.is_contiguous() else ", non-contiguous"))
+        if tuple(t.shape) != shape:
+            raise ValueError("%s of views %s has shape %s, the scene needs %s" % (name, views, tuple(t.shape), shape))
+        return t.detach()
+
+    def add(self, view_ids, outputs, imgs=None, cams=None, rgb=None):
+        """A forward's batch into the stores: one ingest launch on the current stream, no host synchronisation.
+        view_ids: the batch's reference views; outputs: the dictionary CascadeMVSNet.forward returns ("depth" and
+        "photometric_confidence" at (B, H, W), "stage2" / "stage1" confidences at (B, H/2, W/2) / (B, H/4, W/4));
+        imgs: the forward's (B, N, 3, H, W) float32 input, view 0 read in place through the batch stride and stored as
+        uint8(clip(img * 255, 0, 255)) (test_uni.py:285); rgb: instead of imgs, (B, H, W, 3) uint8 decoded images,
+        copied as they are; cams: proj_matrices["stage3"][:, 0] as a host array (B, 2, 4, 4): E = [0], K = [1, :3, :3],
+        what mvsio.write_cam writes and read_camera_parameters reads back (shortest-repr float32 text round-trips
+        exactly). A view without cams cannot be fused, a reference view without colour neither.
+        Raises ValueError, naming the views, before anything is written: map shapes other than (H, W), (H/2, W/2),
+        (H/4, W/4), non-CUDA or non-contiguous tensors, unknown view ids, a view added twice."""
+        view_ids = [int(v) for v in view_ids]
+        B, H, W = len(view_ids), self.H, self.W
+        if not 1 <= B <= _capi.SCENE_MAX_BATCH:
+            raise ValueError("a batch of 1..%d views per call (got %d)" % (_capi.SCENE_MAX_BATCH, B))
+        for v in view_ids:
+            if v not in self.slot:
+                raise ValueError("view %d is not one of the scene's views %s" % (v, self.view_ids))
+            if v in self._added or view_ids.count(v) > 1:
+                raise ValueError("view %d added twice" % v)
+        depth = self._check_map(outputs["depth"], "depth", (B, H, W), view_ids)
+        conf3 = self._check_map(outputs["photometric_confidence"], "photometric_confidence", (B, H, W), view_ids)
+        conf2 = self._check_map(outputs["stage2"]["photometric_confidence"], "stage2 photometric_confidence",
+                                (B, H // 2, W // 2), view_ids)
+        conf1 = self._check_map(outputs["stage1"]["photometric_confidence"], "stage1 photometric_confidence",
+                                (B, H // 4, W // 4), view_ids)
+        if imgs is not None and rgb is not None:
+            raise ValueError("views %s: give imgs or rgb, not both" % view_ids)
+        img_ptr, img_stride = None, 0
+        if imgs is not None:
+            ok = torch.is_tensor(imgs) and imgs.is_cuda and imgs.device == self.depth.device and \
+                imgs.dtype == torch.float32 and imgs.dim() == 5 and tuple(imgs.shape[2:]) == (3, H, W) and \
+                imgs.shape[0] == B and tuple(imgs.stride()[2:]) == (H * W, W, 1)
+            if not ok:
+                raise ValueError("imgs of views %s must be a float32 CUDA tensor (%d, N, 3, %d, %d) with contiguous "
+                                 "images" % (view_ids, B, H, W))
+            img_ptr, img_stride = imgs.data_ptr(), imgs.stride(0) if B > 1 else 0
+        if rgb is not None:
+            rgb = torch.as_tensor(rgb)
+            if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (B, H, W, 3):
+                raise ValueError("rgb of views %s must be uint8 (%d, %d, %d, 3), got %s %s" % (
+                    view_ids, B, H, W, rgb.dtype, tuple(rgb.shape)))
+        if cams is not None:
+            cams = np.array(cams.cpu() if torch.is_tensor(cams) else cams, dtype=np.float32)
+            if cams.shape != (B, 2, 4, 4):
+                raise ValueError("cams of views %s must be (%d, 2, 4, 4), got %s" % (view_ids, B, cams.shape))
+        slots = (ctypes.c_int * B)(*[self.slot[v] for v in view_ids])
+        lib = _capi.load_library()
+        check(lib.damvs_scene_ingest(_capi.stream_ptr(self.depth.device), B, H, W, len(self.view_ids),
+                                     depth.data_ptr(), conf3.data_ptr(), conf2.data_ptr(), conf1.data_ptr(), img_ptr,
+                                     img_stride, slots, self.depth.data_ptr(), self.conf.data_ptr(),
+                                     self.rgb.data_ptr()))
+        if rgb is not None:
+            index = torch.tensor([self.slot[v] for v in view_ids], dtype=torch.int64).to(self.depth.device,
+                                                                                       non_blocking=True)
+            self.rgb.index_copy_(0, index, rgb.to(self.depth.device, non_blocking=True))
+        for b, v in enumerate(view_ids):
+            self._added.add(v)
+            if imgs is not None or rgb is not None:
+                self._coloured.add(v)
+            if cams is not None:
+                self.cams[v] = (cams[b, 1, :3, :3].copy(), cams[b, 0].copy())
+                self._cam_files[v] = cams[b].copy()
+
+    # ------------------------------------------------------------------------------------------------ fuse
+    def _require(self, views, what):
+        for v in views:
+            if v not in self._added:
+                raise ValueError("view %d %s but was never added" % (v, what))
+            if v not in self.cams:
+                raise ValueError("view %d %s but was added without cams" % (v, what))
+
+    def fuse(self, pairs, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25, rel_diff_base=1 / 1300, method="dypcd",
+             thres_view=5, mask_dir=None, max_points=None):
+        """fusion.fuse_scene's per-pair loop over the stores (fusion.fuse_resident): per pair the fusion kernel and
+        compact_cloud on one cursor, one copy of count * 15 bytes, mvsio.write_ply_records. pairs: [(ref view,
+        [source views])] or the path of a pair.txt (read as filter/dypcd.py:84-95 reads it); mask_dir: where the photo /
+        geo / final PNGs go (None: not written). Positions, masks and point order are those of fuse_scene over the
+        files `save` writes, bit for bit; colours too when those images are lossless (the module docstring).
+        A pair that names a view never added raises ValueError and writes no PLY. Returns the point count."""
+        if isinstance(pairs, (str, os.PathLike)):
+            pairs = mvsio.read_pair_file(pairs)
+        pairs = [(int(r), [int(s) for s in src]) for r, src in pairs]
+        for r, src in pairs:
+            self._require([r], "is a reference view of the pair list")
+            self._require(src, "is a source of view %d" % r)
+            if r not in self._coloured:
+                raise ValueError("reference view %d was added without imgs or rgb" % r)
+        used = {v for r, src in pairs for v in [r] + src}
+        refs = {r for r, _ in pairs}
+        depths = {v: self.depth[self.slot[v]] for v in used}
+        confs = {v: tuple(self.conf[self.slot[v], k] for k in range(3)) for v in refs}
+        rgbs = {v: self.rgb[self.slot[v]] for v in refs}
+        return fusion.fuse_resident(pairs, self.cams, depths, confs, rgbs, plyfilename, conf, dist_base, rel_diff_base,
+                                    method, thres_view, mask_dir, max_points, self.depth.device)
+
+    # ------------------------------------------------------------------------------------------------ save
+    def save(self, outdir, scan, lossless=False):
+        """The reference's tree for the views added so far (test_uni.py:265-287), for tools that read it:
+        <outdir>/<scan>/depth_est/%08d.pfm, confidence/%08d{,_stage2,_stage1}.pfm (the bytes mvsio.save_stage_outputs
+        writes), cams/%08d_cam.txt (mvsio.write_cam) and images/%08d.jpg; fusion.fuse_scene(<pair folder>,
+        <outdir>/<scan>, <outdir>/<scan>, ...) reads it back. lossless: PNG data under the .jpg name (readers decode by
+        content), so the colours survive the round trip; otherwise JPEG, as the reference.
+        The stage-1 and stage-2 depth maps (depth_est/%08d_stage{1,2}.pfm in the reference) are not kept in the stores
+        and are not written: nothing downstream reads them."""
+        from PIL import Image
+        root = os.path.join(outdir, scan)
+        for d in ("depth_est", "confidence", "cams", "images"):
+            os.makedirs(os.path.join(root, d), exist_ok=True)
+        for v in self.view_ids:
+            if v not in self._added:
+                continue
+            s = self.slot[v]
+            mvsio.save_pfm(os.path.join(root, "depth_est", "%08d.pfm" % v), self.depth[s].cpu().numpy())
+            c = self.conf[s].cpu().numpy()
+            for k, sfx in enumerate(("", "_stage2", "_stage1")):
+                mvsio.save_pfm(os.path.join(root, "confidence", "%08d%s.pfm" % (v, sfx)), c[k])
+            if v in self._cam_files:
+                mvsio.write_cam(os.path.join(root, "cams", "%08d_cam.txt" % v), self._cam_files[v])
+            if v in self._coloured:
+                Image.fromarray(self.rgb[s].cpu().numpy()).save(os.path.join(root, "images", "%08d.jpg" % v),
+                                                                format="PNG" if lossless else "JPEG")
+
+
+def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192, interval_scale=1.06, max_h=1184,
+                      max_w=1600, batch=4, streams=1, **fuse_kwargs):
+    """One scan from its directory (<datapath>/<scan>/{pair.txt, cams/, images/}) to a fused PLY without the disk in
+    between: mvsio.EvalScenes samples in batches of `batch` reference views through `model` (a CascadeMVSNet on a HIP
+    device; `streams` as in its forward) with check_range=False, each batch into a SceneMaps, one
+    model.DepthNet.check_range() after the last batch, then SceneMaps.fuse over the scan's pair.txt with
+    `fuse_kwargs` (conf, dist_base, rel_diff_base, method, thres_view, mask_dir, max_points). Every image of the scan is
+    decoded and scaled once (EvalScenes' cache_views). All views must come out at one size. Returns the point count.
+    Colours are taken before the reference's JPEG re-encoding (the module docstring)."""
+    ds = mvsio.EvalScenes(datapath, [scan], nviews, ndepths=ndepths, interval_scale=interval_scale, max_h=max_h,
+                          max_w=max_w, cache_views=True)
+    device = next(model.parameters()).device
+    refs = [ref for _, ref, _ in ds.metas]
+    maps = None
+    with torch.no_grad():
+        for i0 in range(0, len(ds), batch):
+            items = [ds[i] for i in range(i0, min(i0 + batch, len(ds)))]
+            shapes = {it["imgs"].shape for it in items}
+            if len(shapes) != 1 or (maps is not None and next(iter(shapes))[2:] != (maps.H, maps.W)):
+                raise ValueError("views %s of %s come out at sizes %s: one scene, one size" % (
+                    refs[i0:i0 + len(items)], scan, sorted(shapes)))
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            imgs = up(np.stack([it["imgs"] for it in items]))
+            proj_host = {k: np.stack([it["proj_matrices"][k] for it in items]) for k in items[0]["proj_matrices"]}
+            proj = {k: up(v) for k, v in proj_host.items()}
+            depth_values = up(np.stack([it["depth_values"] for it in items]))
+            ins = {k: up(np.stack([it["intrinsics_matrices"][k] for it in items]))
+                   for k in items[0]["intrinsics_matrices"]}
+            if maps is None:
+                maps = SceneMaps(refs, imgs.shape[3], imgs.shape[4], device)
+            out = model(imgs, proj, depth_values, ins, streams=streams, check_range=False)
+            maps.add(refs[i0:i0 + len(items)], out, imgs=imgs, cams=proj_host["stage3"][:, 0])
+    model.DepthNet.check_range()
+    return maps.fuse(os.path.join(datapath, scan, "pair.txt"), plyfilename, **fuse_kwargs)

@@ -346,6 +346,33 @@ int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, co
                        unsigned int* scratch, long long scratch_elems, unsigned char* records, long long capacity,
                        unsigned long long* cursor);
 
+/* ------------------------------------------------------------------ scene ingest (f4)
+ * The outputs of one forward over B reference views, written into scene-resident stores that the fusion entry points
+ * above read in place. It replaces the host path of test_uni.py:246-287 (maps to the host, cv2.INTER_NEAREST resize of
+ * the stage-1 / stage-2 confidences, PFM files, the reference image as (img * 255).astype(uint8)) and the reader side
+ * filter/dypcd.py:198-209 (the files read back and uploaded). Inputs, device fp32, contiguous: depth and conf3
+ * [B][H][W] (final stage), conf2 [B][H/2][W/2], conf1 [B][H/4][W/4]; img: sample b's reference image at
+ * img + b * img_batch_stride floats, three planes (red, green, blue) of H * W floats, so view 0 of a (B, N, 3, H, W)
+ * batch is read in place with img_batch_stride = N * 3 * H * W; NULL: rgb_store is not written (and may be NULL).
+ * Stores, device, V views of one size; sample b goes to slot s = slots[b]:
+ *   depth_store [V][H][W] fp32            depth_store[s] = depth[b]
+ *   conf_store  [V][3][H][W] fp32         the order damvs_fusion_view takes: [s][0] = conf3[b],
+ *                                         [s][1][y][x] = conf2[b][y >> 1][x >> 1], [s][2][y][x] = conf1[b][y >> 2][x >> 2]
+ *                                         (INTER_NEAREST at exactly x2 and x4)
+ *   rgb_store   [V][H][W][3] uint8        [s][y][x][c] = uint8(trunc(clip(img[b][c][y][x] * 255.0f, 0, 255))): one fp32
+ *                                         multiply rounded to nearest, clamp, truncation, as numpy computes it in float32
+ * slots is a HOST array of B distinct entries in [0, V); it is copied into the kernel arguments, so the call needs no
+ * device memory of its own, does not synchronise, and can be captured into a graph. One launch on `stream`; slots not
+ * named are not touched.
+ * Errors (before any device work): a null pointer other than img (rgb_store may be null only when img is), a slot
+ * outside [0, V) or repeated, a full-size map or store not 16-byte aligned (conf2: 8, rgb_store: 4), img_batch_stride
+ * not a multiple of 4 -> DAMVS_E_ARG; B outside 1..DAMVS_SCENE_MAX_BATCH, H or W not a positive multiple of 4, V < 1,
+ * H * W * 12 >= 2^31 -> DAMVS_E_SHAPE. */
+#define DAMVS_SCENE_MAX_BATCH 64
+int damvs_scene_ingest(void* stream, int B, int H, int W, int V, const float* depth, const float* conf3,
+                       const float* conf2, const float* conf1, const float* img, long long img_batch_stride,
+                       const int* slots, float* depth_store, float* conf_store, unsigned char* rgb_store);
+
 #ifdef __cplusplus
 }
 #endif
