@@ -291,14 +291,15 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #ifndef DAMVS_BUILD_ID
 #define DAMVS_BUILD_ID "unstamped"
 #endif
-// The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so) carry the same
-// one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
+// The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so,
+// libdamvs_inputs.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
   static const std::string id = [] {
     std::string s(DAMVS_BUILD_ID);
     const std::pair<const char*, const char*> side[] = {{"libdamvs_fusion.so", fusion_static_build_id()},
                                                         {"libdamvs_cloud.so", fusion_cloud_build_id()},
-                                                        {"libdamvs_scene.so", scene_build_id()}};
+                                                        {"libdamvs_scene.so", scene_build_id()},
+                                                        {"libdamvs_inputs.so", inputs_build_id()}};
     for (const auto& l : side)
       if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
     return s;
@@ -1014,6 +1015,37 @@ int damvs_scene_ingest(void* stream, int B, int H, int W, int V, const float* de
   a.conf_store = conf_store;
   a.rgb_store = img ? rgb_store : nullptr;
   return hip_check(launch_scene_ingest(static_cast<hipStream_t>(stream), B, a), "scene_ingest launch");
+}
+
+// ============================================================================ scene inputs
+int damvs_scene_inputs(void* stream, int n_images, int H0, int W0, int H, int W, int V, const unsigned char* rgb_store,
+                       const int* slots, float* out) {
+  if (!rgb_store) return fail(DAMVS_E_ARG, "null rgb_store");
+  if (!slots) return fail(DAMVS_E_ARG, "null slots");
+  if (!out) return fail(DAMVS_E_ARG, "null out");
+  if (n_images < 1 || n_images > kInputsMaxImages)
+    return fail(DAMVS_E_ARG, "n_images %d not in [1, %d]", n_images, kInputsMaxImages);
+  if (H0 < 1 || W0 < 1) return fail(DAMVS_E_ARG, "H0 x W0 = %d x %d: a size below 1", H0, W0);
+  if (H < 1 || W < 1) return fail(DAMVS_E_ARG, "H x W = %d x %d: a size below 1", H, W);
+  if (V < 1) return fail(DAMVS_E_ARG, "V %d < 1", V);
+  if (W % 4) return fail(DAMVS_E_ARG, "W %d is not a multiple of 4", W);
+  // the offsets within an image are 32-bit
+  if (3LL * H0 * W0 >= (1LL << 31)) return fail(DAMVS_E_ARG, "H0 x W0 = %d x %d: 3 * H0 * W0 >= 2^31", H0, W0);
+  if (3LL * H * W >= (1LL << 31)) return fail(DAMVS_E_ARG, "H x W = %d x %d: 3 * H * W >= 2^31", H, W);
+  if (reinterpret_cast<uintptr_t>(out) & 15) return fail(DAMVS_E_ARG, "out is not 16-byte aligned");
+  InputsArgs a;
+  for (int i = 0; i < n_images; ++i) {
+    if (slots[i] < 0 || slots[i] >= V) return fail(DAMVS_E_ARG, "slot %d of image %d outside [0, %d)", slots[i], i, V);
+    a.slots[i] = slots[i];
+  }
+  for (int i = n_images; i < kInputsMaxImages; ++i) a.slots[i] = 0;
+  a.H0 = H0;
+  a.W0 = W0;
+  a.H = H;
+  a.W = W;
+  a.rgb_store = rgb_store;
+  a.out = out;
+  return hip_check(launch_scene_inputs(static_cast<hipStream_t>(stream), n_images, a), "scene_inputs launch");
 }
 
 }  // extern "C"

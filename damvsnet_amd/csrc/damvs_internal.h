@@ -225,6 +225,19 @@ struct SceneArgs {
 hipError_t launch_scene_ingest(hipStream_t s, int B, const SceneArgs& a);
 const char* scene_build_id();
 
+// ---------------------------------------------------------------- scene inputs (k_inputs.hip, libdamvs_inputs.so)
+constexpr int kInputsMaxImages = 128;                 // DAMVS_INPUTS_MAX_IMAGES: the slot table lives in the kernel arguments
+constexpr int kInputsBlockX = 64, kInputsBlockY = 4;  // threads: 64 groups of 4 output pixels across, 4 rows
+struct InputsArgs {
+  int H0, W0;                       // size of the stored images, 3 * H0 * W0 < 2^31
+  int H, W;                         // size of the output images, W a multiple of 4, 3 * H * W < 2^31
+  const unsigned char* rgb_store;   // [V][H0][W0][3]
+  float* out;                       // [n_images][3][H][W], 16-byte aligned
+  int slots[kInputsMaxImages];      // image i -> slot
+};
+hipError_t launch_scene_inputs(hipStream_t s, int n_images, const InputsArgs& a);
+const char* inputs_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -161,6 +161,12 @@ def scale_mvs_input(img, intrinsics, max_w, max_h, base=32):
     """datasets/general_eval.py:89-108: shrink to fit (max_w, max_h) keeping the aspect ratio, round
     both sides down to a multiple of `base`, scale K's rows accordingly."""
     h, w = img.shape[:2]
+    new_w, new_h, intrinsics = scale_mvs_camera(h, w, intrinsics, max_w, max_h, base)
+    return resize_bilinear(img, new_w, new_h), intrinsics
+
+
+def scale_mvs_camera(h, w, intrinsics, max_w, max_h, base=32):
+    """scale_mvs_input without the pixels: an (h, w) image's working size and its scaled K -> (new_w, new_h, K)."""
     if h > max_h or w > max_w:
         scale = 1.0 * max_h / h
         if scale * w > max_w:
@@ -171,13 +177,20 @@ def scale_mvs_input(img, intrinsics, max_w, max_h, base=32):
     intrinsics = intrinsics.copy()
     intrinsics[0, :] *= 1.0 * new_w / w
     intrinsics[1, :] *= 1.0 * new_h / h
-    return resize_bilinear(img, int(new_w), int(new_h)), intrinsics
+    return int(new_w), int(new_h), intrinsics
 
 
 def read_img(filename):
     """RGB image as float32 in [0, 1] (datasets/general_eval.py:83-87)."""
     from PIL import Image
     return np.array(Image.open(filename), dtype=np.float32) / 255.0
+
+
+def read_img_bytes(filename):
+    """The image as decoded, without conversion: (H, W, 3) uint8 for an RGB file (scene.SceneInputs.put refuses
+    anything else). read_img is this array as float32 / 255."""
+    from PIL import Image
+    return np.array(Image.open(filename))
 
 
 # ------------------------------------------------------------------------------ eval samples
@@ -260,6 +273,44 @@ class EvalScenes:
         return {"imgs": np.stack(imgs).transpose(0, 3, 1, 2), "proj_matrices": stage_projections(projs),
                 "depth_values": depth_values, "intrinsics_matrices": ins,
                 "filename": scan + "/{}/" + "%08d" % view_ids[0] + "{}"}
+
+    def cameras(self, idx):
+        """Item idx without the pixels, for a caller that keeps the scene's images elsewhere (scene.SceneInputs):
+        what __getitem__ returns minus "imgs" (proj_matrices, depth_values and intrinsics_matrices are the same
+        bits), plus "view_ids" (reference view first), "size" (H, W), the working size of every view, and
+        "original_size" (H0, W0), the size of every view's file. Only the header of an image file is read.
+        ValueError if the views' files differ in size (files of one size come out at one working size, so this is also
+        the case of a view whose working size differs from the reference view's): __getitem__ resizes such a view
+        twice, which one resize from the original does not equal. A dataset with fix_res is refused for the same
+        reason."""
+        from PIL import Image
+        if self.fix_res or self.fix_wh:
+            raise ValueError("cameras() serves datasets without fix_res")
+        scan, ref_view, src_views = self.metas[idx]
+        view_ids = [ref_view] + src_views[:self.nviews - 1]
+        projs, depth_values, K, size, original = [], None, None, None, None
+        for i, vid in enumerate(view_ids):
+            with Image.open(self._img_path(scan, vid)) as im:
+                w0, h0 = im.size
+            K, E, dmin, dint = read_cam_file(os.path.join(self.datapath, scan, "cams", "%08d_cam.txt" % vid),
+                                             self.ndepths, self.interval_scale[scan])
+            new_w, new_h, K = scale_mvs_camera(h0, w0, K, self.max_w, self.max_h)
+            if i == 0:
+                size, original = (new_h, new_w), (h0, w0)
+                depth_values = np.arange(dmin, dint * (self.ndepths - 0.5) + dmin, dint, dtype=np.float32)
+            if (h0, w0) != original:
+                raise ValueError("view %d of %s is %d x %d, its reference view %d is %d x %d: one scene, one size" % (
+                    vid, scan, h0, w0, ref_view, original[0], original[1]))
+            pm = np.zeros((2, 4, 4), dtype=np.float32)
+            pm[0] = E
+            pm[1, :3, :3] = K
+            projs.append(pm)
+        ins = {"stage1": K, "stage2": K.copy(), "stage3": K.copy()}  # K of the last view, as __getitem__
+        ins["stage2"][:2, :] = K[:2, :] * 2.0
+        ins["stage3"][:2, :] = K[:2, :] * 4.0
+        return {"proj_matrices": stage_projections(np.stack(projs)), "depth_values": depth_values,
+                "intrinsics_matrices": ins, "filename": scan + "/{}/" + "%08d" % view_ids[0] + "{}",
+                "view_ids": view_ids, "size": size, "original_size": original}
 
 
 # ------------------------------------------------------------------------------------- outputs

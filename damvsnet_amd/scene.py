@@ -10,12 +10,17 @@ reference image as uint8 HWC. `SceneMaps.fuse` runs fusion.fuse_scene's per-pair
 (fusion.fuse_resident), `SceneMaps.save` writes the reference's tree for tools that want the files, and
 `reconstruct_scene` drives the whole path for one scan.
 
+The other end of the forward (row f3): `SceneInputs` keeps the scan's decoded images on the device as uint8, each view
+uploaded once, and writes the forward's `imgs` for a batch by one HIP launch (k_inputs.hip, damvs_scene_inputs) in
+place of the host's float conversion, resize, stack and per-batch float32 upload (`reconstruct_scene(inputs="device")`).
+
 A stated difference: the reference re-encodes the reference image as JPEG (test_uni.py:286-287) and the fusion reads
 that file back, so its colours carry JPEG loss. The in-memory path takes the colour before the JPEG. Positions, masks
 and point order are those of the file path bit for bit; colours are equal whenever the file path's images are lossless.
 """
 from __future__ import annotations
 
+import concurrent.futures as cf
 import ctypes
 import os
 
@@ -183,29 +188,133 @@ class SceneMaps:
                                                                 format="PNG" if lossless else "JPEG")
 
 
+class SceneInputs:
+    """The decoded images of a scene's views, resident on the device as the bytes they were decoded to, and the
+    forward's `imgs` tensor from them: `store` (V, H0, W0, 3) uint8 on `device`, view i of `view_ids` in slot i, and
+    `mirror`, a host array of the same shape (pinned when the device is a GPU: the whole mirror, so no staging buffer
+    is ever reused under an upload that is still in flight). `put` uploads a view once; `batch` is one launch of
+    damvs_scene_inputs (k_inputs.hip), which converts to float32 in [0, 1], resizes to the working size H x W and
+    writes planar images (include/damvs.h states the arithmetic)."""
+
+    def __init__(self, view_ids, H0, W0, H, W, device="cuda"):
+        view_ids = [int(v) for v in view_ids]
+        if len(set(view_ids)) != len(view_ids) or not view_ids:
+            raise ValueError("view_ids must be a non-empty list of distinct view ids")
+        if min(H0, W0, H, W) < 1 or W % 4:
+            raise ValueError("sizes of at least 1 and W a multiple of 4 (got %d x %d -> %d x %d)" % (H0, W0, H, W))
+        self.view_ids, self.device = view_ids, torch.device(device)
+        self.H0, self.W0, self.H, self.W = int(H0), int(W0), int(H), int(W)
+        self.slot = {v: i for i, v in enumerate(view_ids)}
+        shape = (len(view_ids), self.H0, self.W0, 3)
+        self.store = torch.empty(shape, device=self.device, dtype=torch.uint8)
+        self.mirror = torch.empty(shape, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
+        self._put = set()
+
+    def put(self, view_id, rgb):
+        """A decoded view, (H0, W0, 3) uint8, into its slot: copied into the mirror, then one non-blocking upload of
+        that slice on the current stream. ValueError, naming the view: an unknown view, a view put twice, another
+        shape or dtype (grey and RGBA images are refused, not converted)."""
+        view_id = int(view_id)
+        if view_id not in self.slot:
+            raise ValueError("view %d is not one of the scene's views %s" % (view_id, self.view_ids))
+        if view_id in self._put:
+            raise ValueError("view %d put twice" % view_id)
+        rgb = np.asarray(rgb)
+        if rgb.dtype != np.uint8 or rgb.shape != (self.H0, self.W0, 3):
+            raise ValueError("view %d must be a uint8 image (%d, %d, 3), got %s %s" % (
+                view_id, self.H0, self.W0, rgb.dtype, rgb.shape))
+        s = self.slot[view_id]
+        self.mirror[s].numpy()[...] = rgb
+        self.store[s].copy_(self.mirror[s], non_blocking=True)
+        self._put.add(view_id)
+
+    def batch(self, views, out=None):
+        """views: B lists of N view ids, the reference view first -> the forward's (B, N, 3, H, W) float32 `imgs`, by
+        one damvs_scene_inputs launch on the current stream (no allocation when `out` is given and fits: a contiguous
+        float32 tensor on the device with at least B * N * 3 * H * W elements, whose leading part is returned in that
+        shape). ValueError: a view that was never put, lists of different lengths, B * N outside
+        1..DAMVS_INPUTS_MAX_IMAGES."""
+        views = [[int(v) for v in sample] for sample in views]
+        B, N = len(views), len(views[0]) if views else 0
+        if any(len(sample) != N for sample in views):
+            raise ValueError("ragged view lists %s: every sample needs the same number of views" % views)
+        n = B * N
+        if not 1 <= n <= _capi.INPUTS_MAX_IMAGES:
+            raise ValueError("a batch of 1..%d images per call (got %d x %d)" % (_capi.INPUTS_MAX_IMAGES, B, N))
+        for v in (v for sample in views for v in sample):
+            if v not in self._put:
+                raise ValueError("view %d was never put" % v)
+        need = n * 3 * self.H * self.W
+        fits = torch.is_tensor(out) and out.dtype == torch.float32 and out.device == self.store.device and \
+            out.is_contiguous() and out.numel() >= need
+        imgs = out.view(-1)[:need].view(B, N, 3, self.H, self.W) if fits else \
+            torch.empty(B, N, 3, self.H, self.W, device=self.device, dtype=torch.float32)
+        slots = (ctypes.c_int * n)(*[self.slot[v] for sample in views for v in sample])
+        lib = _capi.load_library()
+        check(lib.damvs_scene_inputs(_capi.stream_ptr(self.store.device), n, self.H0, self.W0, self.H, self.W,
+                                     len(self.view_ids), self.store.data_ptr(), slots, imgs.data_ptr()))
+        return imgs
+
+
+def _device_batches(ds, scan, batch, device, decode_workers):
+    """reconstruct_scene's inputs="device": every view of the scan decoded in `decode_workers` threads and put into a
+    SceneInputs as soon as it is ready, then per batch of `batch` samples (the samples without pixels, `imgs` in one
+    reused buffer)."""
+    samples = [ds.cameras(i) for i in range(len(ds))]
+    sizes = sorted({s["original_size"] for s in samples})
+    if len(sizes) != 1:
+        raise ValueError("the images of %s have sizes %s: one scene, one size" % (scan, sizes))
+    (H0, W0), (H, W) = sizes[0], samples[0]["size"]
+    store = SceneInputs(sorted({v for s in samples for v in s["view_ids"]}), H0, W0, H, W, device)
+    with cf.ThreadPoolExecutor(decode_workers) as pool:
+        decoding = {pool.submit(mvsio.read_img_bytes, ds._img_path(scan, v)): v for v in store.view_ids}
+        for done in cf.as_completed(decoding):
+            store.put(decoding[done], done.result())
+    reused = None
+    for i0 in range(0, len(samples), batch):
+        items = samples[i0:i0 + batch]
+        imgs = store.batch([it["view_ids"] for it in items], out=reused)
+        reused = imgs if reused is None else reused  # the first batch is the largest
+        yield items, imgs
+
+
 def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192, interval_scale=1.06, max_h=1184,
-                      max_w=1600, batch=4, streams=1, **fuse_kwargs):
+                      max_w=1600, batch=4, streams=1, inputs="host", decode_workers=4, **fuse_kwargs):
     """One scan from its directory (<datapath>/<scan>/{pair.txt, cams/, images/}) to a fused PLY without the disk in
     between: mvsio.EvalScenes samples in batches of `batch` reference views through `model` (a CascadeMVSNet on a HIP
     device; `streams` as in its forward) with check_range=False, each batch into a SceneMaps, one
     model.DepthNet.check_range() after the last batch, then SceneMaps.fuse over the scan's pair.txt with
     `fuse_kwargs` (conf, dist_base, rel_diff_base, method, thres_view, mask_dir, max_points). Every image of the scan is
     decoded and scaled once (EvalScenes' cache_views). All views must come out at one size. Returns the point count.
-    Colours are taken before the reference's JPEG re-encoding (the module docstring)."""
+    Colours are taken before the reference's JPEG re-encoding (the module docstring).
+    inputs: "host" converts, resizes and stacks the images with numpy and torch on the CPU and uploads every batch as
+    float32. "device" decodes the views to uint8 in `decode_workers` threads, uploads each once into a SceneInputs as
+    soon as it is decoded and lets one launch per batch write `imgs` into one reused buffer; the cameras come from
+    EvalScenes.cameras. The two agree bit for bit when the images need no resize; a resized image differs from the
+    host's in its last bits (at most 2^-21: tests/test_inputs.py), so the depth maps may too. The device path needs
+    image files of one size and raises ValueError otherwise."""
+    if inputs not in ("host", "device"):
+        raise ValueError("inputs must be \"host\" or \"device\" (got %r)" % (inputs,))
+    if not isinstance(decode_workers, int) or decode_workers < 1:
+        raise ValueError("decode_workers must be a positive integer (got %r)" % (decode_workers,))
     ds = mvsio.EvalScenes(datapath, [scan], nviews, ndepths=ndepths, interval_scale=interval_scale, max_h=max_h,
                           max_w=max_w, cache_views=True)
     device = next(model.parameters()).device
     refs = [ref for _, ref, _ in ds.metas]
     maps = None
+    device_batches = _device_batches(ds, scan, batch, device, decode_workers) if inputs == "device" else None
     with torch.no_grad():
         for i0 in range(0, len(ds), batch):
-            items = [ds[i] for i in range(i0, min(i0 + batch, len(ds)))]
-            shapes = {it["imgs"].shape for it in items}
-            if len(shapes) != 1 or (maps is not None and next(iter(shapes))[2:] != (maps.H, maps.W)):
-                raise ValueError("views %s of %s come out at sizes %s: one scene, one size" % (
-                    refs[i0:i0 + len(items)], scan, sorted(shapes)))
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            imgs = up(np.stack([it["imgs"] for it in items]))
+            if device_batches is not None:
+                items, imgs = next(device_batches)
+            else:
+                items = [ds[i] for i in range(i0, min(i0 + batch, len(ds)))]
+                shapes = {it["imgs"].shape for it in items}
+                if len(shapes) != 1 or (maps is not None and next(iter(shapes))[2:] != (maps.H, maps.W)):
+                    raise ValueError("views %s of %s come out at sizes %s: one scene, one size" % (
+                        refs[i0:i0 + len(items)], scan, sorted(shapes)))
+                imgs = up(np.stack([it["imgs"] for it in items]))
             proj_host = {k: np.stack([it["proj_matrices"][k] for it in items]) for k in items[0]["proj_matrices"]}
             proj = {k: up(v) for k, v in proj_host.items()}
             depth_values = up(np.stack([it["depth_values"] for it in items]))

@@ -373,6 +373,30 @@ int damvs_scene_ingest(void* stream, int B, int H, int W, int V, const float* de
                        const float* conf2, const float* conf1, const float* img, long long img_batch_stride,
                        const int* slots, float* depth_store, float* conf_store, unsigned char* rgb_store);
 
+/* ------------------------------------------------------------------ scene inputs (f3)
+ * The forward's `imgs` tensor for a batch, written from the scene's decoded images, which stay on the device as the
+ * bytes they were decoded to. It replaces the host path of datasets/general_eval.py:83-108 (np.array(img, float32) /
+ * 255, the resize to the working size) and the upload of B * N float32 images per batch.
+ *   rgb_store [V][H0][W0][3] uint8, device: V decoded views of one size
+ *   out       [n_images][3][H][W] fp32, device: out[i] is view slots[i] as float32 in [0, 1], resized to H x W, planar;
+ *             with n_images = B * N and i = b * N + n it is the contiguous (B, N, 3, H, W) tensor of the forward
+ * Arithmetic, all float32, every operation rounded to nearest on its own: p = float(byte) / 255; per axis with n_in
+ * source and n_out output samples scale = float(n_in) / float(n_out), src = max(fma(scale, float(d) + 0.5f, -0.5f), 0)
+ * (one rounding for the multiply-add), i0 = min(int(src), n_in - 1), i1 = min(i0 + 1, n_in - 1), l1 = src - float(i0),
+ * l0 = 1 - l1; out = a0 * (b0 * p00 + b1 * p01) + a1 * (b0 * p10 + b1 * p11) with a the row and b the column weights:
+ * bilinear interpolation with half-pixel centres and clamped borders (torch's F.interpolate, align_corners=False, as
+ * its CPU kernel computes it; tests/inputs_statement.py states it in numpy). At H == H0 and W == W0 the output is
+ * float(byte) / 255 exactly.
+ * slots is a HOST array of n_images entries in [0, V), which may repeat; it is copied into the kernel arguments, so the
+ * call needs no device memory of its own, does not synchronise, and can be captured into a graph. One launch on
+ * `stream`.
+ * Errors (before any device work), all DAMVS_E_ARG with a message that names the argument: a null pointer, n_images
+ * outside 1..DAMVS_INPUTS_MAX_IMAGES, a size below 1, W not a multiple of 4, out not 16-byte aligned, a slot outside
+ * [0, V), 3 * H0 * W0 or 3 * H * W >= 2^31. */
+#define DAMVS_INPUTS_MAX_IMAGES 128
+int damvs_scene_inputs(void* stream, int n_images, int H0, int W0, int H, int W, int V,
+                       const unsigned char* rgb_store, const int* slots, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """Scene reconstruction, scene directory to PLY: the file path against the in-memory path (damvsnet_amd/scene.py).
 
-  python tools/bench_scene.py [--views 11 --H 1184 --W 1600 --nviews 5 --batch 4 --repeats 5 --out F]
+  python tools/bench_scene.py [--views 11 --H 1184 --W 1600 --H0 H --W0 W --nviews 5 --batch 4 --repeats 5 --out F]
 
 One process, one bf16 model with synthetic weights (bench.py's build_model), one scene written by the tool: --views
 views at H x W with lossless images (PNG data under .jpg names) of uniform noise, DTU-like cameras (synth.cameras) and a
@@ -8,15 +8,23 @@ pair.txt in which every view lists all the others. Wall clock from the loaded mo
   (a) files   EvalScenes -> forward -> mvsio.save_stage_outputs, write_cam and the image per view ->
               fusion.fuse_scene(save_masks=False): the reference's directory contract (test_uni.py:229-287, then the
               filter), with the fusion already on the device;
-  (b) memory  scene.reconstruct_scene.
-One warm-up of each, then --repeats runs of each, interleaved; the median and the spread of each and the ratio (b) / (a)
-of the medians. The two PLYs are asserted byte-identical (the images are lossless). With synthetic weights the depth
+  (b) memory  scene.reconstruct_scene;
+  (c) device  scene.reconstruct_scene(inputs="device"): the views decoded to uint8 in threads, uploaded once each,
+              converted, resized and batched by damvs_scene_inputs.
+One warm-up of each, then --repeats runs of each, interleaved; the median and the spread of each and the ratios (b) / (a)
+and (c) / (b) of the medians. The PLYs of (a) and (b) are asserted byte-identical (the images are lossless), and (c)'s
+too when the scene needs no resize (--H0 x --W0, the size of the image files, equal to the working size, the default);
+otherwise the `imgs` of (c)'s and (b)'s first batch are asserted to agree within 2^-21 (tests/test_inputs.py). With synthetic weights the depth
 maps are noise and the cloud is small or empty: the tool measures the plumbing around the forward, which is the same
 work for any weights, and not the fusion kernels (tools/bench_fusion.py does).
 
 Then the ingest launch alone (damvs_scene_ingest at B = 4 into a store of --views slots): 20 back-to-back calls per
 block between two HIP events, median of 5 blocks, with the bytes it moves (reads: depth, three confidences at full,
 half and quarter size and three image planes; writes: depth, three confidences, 3 colour bytes per pixel) and GB/s.
+Then the inputs launch alone (damvs_scene_inputs, B * N = 20 images of 1200 x 1600 to 1184 x 1568, what
+scale_mvs_input gives DTU, from a store of --views slots), timed the same way, and a one-off breakdown of (b)'s wall
+clock (`breakdown`): the same steps as reconstruct_scene's host path, one run, with a device synchronisation after
+every device step so that each step's time is its own; the sum is therefore a little above an unsynchronised run.
 One JSON line, appended to --out when given.
 """
 import argparse
@@ -87,9 +95,121 @@ def file_path(net, data, scan, out_dir, ply, a):
     return fusion.fuse_scene(os.path.join(data, scan), scan_out, scan_out, ply, save_masks=False)
 
 
-def memory_path(net, data, scan, ply, a):
+def memory_path(net, data, scan, ply, a, inputs="host"):
     from damvsnet_amd import scene
-    return scene.reconstruct_scene(net, data, scan, ply, nviews=a.nviews, max_h=a.H, max_w=a.W, batch=a.batch)
+    return scene.reconstruct_scene(net, data, scan, ply, nviews=a.nviews, max_h=a.H, max_w=a.W, batch=a.batch,
+                                   inputs=inputs)
+
+
+def breakdown(net, data, scan, ply, a):
+    """(b)'s steps, one run, each timed on its own: what reconstruct_scene(inputs="host") does through
+    mvsio.EvalScenes(cache_views=True), restated step by step (every view of the scene has one size here, so the
+    dataset's second resize never happens). read_img decodes straight into float32; here the decode to uint8 and the
+    conversion are separate steps, which costs one more pass over the bytes."""
+    from PIL import Image
+    from damvsnet_amd import mvsio
+    from damvsnet_amd.scene import SceneMaps
+    t = {k: 0.0 for k in ("decode", "convert", "resize", "cameras", "stack", "upload", "forward", "ingest", "fuse")}
+
+    def timed(name, fn, sync=False):
+        t0 = time.perf_counter()
+        r = fn()
+        if sync:
+            torch.cuda.synchronize()
+        t[name] += time.perf_counter() - t0
+        return r
+
+    torch.cuda.synchronize()
+    start = time.perf_counter()
+    ds = mvsio.EvalScenes(data, [scan], a.nviews, max_h=a.H, max_w=a.W)
+    refs = [ref for _, ref, _ in ds.metas]
+    views, maps, largest = {}, None, 0
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    with torch.no_grad():
+        for i0 in range(0, len(ds), a.batch):
+            imgs_b, proj_b, dv_b, ins_b = [], [], [], []
+            for _, ref, src in ds.metas[i0:i0 + a.batch]:
+                ids = [ref] + src[:a.nviews - 1]
+                for v in ids:
+                    if v not in views:
+                        raw = timed("decode", lambda: np.array(Image.open(ds._img_path(scan, v))))
+                        img = timed("convert", lambda: raw.astype(np.float32) / 255.0)
+                        cam = timed("cameras", lambda: mvsio.read_cam_file(
+                            os.path.join(data, scan, "cams", "%08d_cam.txt" % v), ds.ndepths, ds.interval_scale[scan]))
+                        img, K = timed("resize", lambda: mvsio.scale_mvs_input(img, cam[0], a.W, a.H))
+                        views[v] = (img, K) + cam[1:]
+                pm = np.zeros((len(ids), 2, 4, 4), np.float32)
+                for n, v in enumerate(ids):
+                    pm[n, 0], pm[n, 1, :3, :3] = views[v][2], views[v][1]
+                imgs_b.append(timed("stack", lambda: np.stack([views[v][0] for v in ids]).transpose(0, 3, 1, 2)))
+                proj_b.append(mvsio.stage_projections(pm))
+                _, K, _, dmin, dint = views[ids[-1]][:2] + views[ids[0]][2:]
+                dv_b.append(np.arange(dmin, dint * (ds.ndepths - 0.5) + dmin, dint, dtype=np.float32))
+                ins_b.append({"stage%d" % (k + 1): np.concatenate([K[:2] * 2.0 ** k, K[2:]]) for k in range(3)})
+            stacked = timed("stack", lambda: np.ascontiguousarray(np.stack(imgs_b)))
+            imgs = timed("upload", lambda: torch.from_numpy(stacked).cuda(), sync=True)
+            largest = max(largest, stacked.nbytes)
+            proj_host = {k: np.stack([p[k] for p in proj_b]) for k in proj_b[0]}
+            proj = {k: up(v) for k, v in proj_host.items()}
+            ins = {k: up(np.stack([i[k] for i in ins_b])) for k in ins_b[0]}
+            dv = up(np.stack(dv_b))
+            out = timed("forward", lambda: net(imgs, proj, dv, ins, check_range=False), sync=True)
+            if maps is None:
+                maps = SceneMaps(refs, imgs.shape[3], imgs.shape[4], "cuda")
+            timed("ingest", lambda: maps.add(refs[i0:i0 + len(imgs_b)], out, imgs=imgs, cams=proj_host["stage3"][:, 0]),
+                  sync=True)
+    net.DepthNet.check_range()
+    n = timed("fuse", lambda: maps.fuse(os.path.join(data, scan, "pair.txt"), ply), sync=True)
+    total = time.perf_counter() - start
+    res = {k: round(v, 4) for k, v in t.items()}
+    res.update(total_s=round(total, 4), other_s=round(total - sum(t.values()), 4), points=n,
+               largest_batch_MB=round(largest / 1e6, 1))
+    return res
+
+
+def inputs_bench(a, calls=20, blocks=5):
+    """damvs_scene_inputs alone at DTU's sizes: B * N = 20 images per call."""
+    from damvsnet_amd import _capi
+    lib = _capi.load_library()
+    n, H0, W0, H, W, V = 20, 1200, 1600, 1184, 1568, a.views
+    g = torch.Generator(device="cuda").manual_seed(0)
+    store = torch.randint(0, 256, (V, H0, W0, 3), device="cuda", dtype=torch.uint8, generator=g)
+    out = torch.empty(n, 3, H, W, device="cuda")
+    slots = (ctypes.c_int * n)(*[(3 * i + 1) % V for i in range(n)])
+    call = lambda: _capi.check(lib.damvs_scene_inputs(_capi.stream_ptr(), n, H0, W0, H, W, V, store.data_ptr(), slots,
+                                                      out.data_ptr()))
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(blocks):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / calls)
+    read, written = n * 3 * H0 * W0, n * 3 * H * W * 4  # every source byte once per image that lists it; the output
+    med = float(np.median(ms))
+    return {"images": n, "from": [H0, W0], "to": [H, W], "calls_per_block": calls,
+            "ms_per_call_blocks": [round(m, 4) for m in ms], "ms_per_call": round(med, 4), "bytes_read": read,
+            "bytes_written": written, "GBps": round((read + written) / med / 1e6, 1)}
+
+
+def first_batch_imgs_diff(data, scan, a):
+    """max |imgs of (c) - imgs of (b)| over the first batch, when the scene needs a resize."""
+    from damvsnet_amd import mvsio
+    from damvsnet_amd.scene import SceneInputs
+    ds = mvsio.EvalScenes(data, [scan], a.nviews, max_h=a.H, max_w=a.W, cache_views=True)
+    n = min(a.batch, len(ds))
+    want = torch.from_numpy(np.stack([ds[i]["imgs"] for i in range(n)]))
+    cams = [ds.cameras(i) for i in range(n)]
+    ids = sorted({v for c in cams for v in c["view_ids"]})
+    si = SceneInputs(ids, *cams[0]["original_size"], *cams[0]["size"], "cuda")
+    for v in ids:
+        si.put(v, mvsio.read_img_bytes(ds._img_path(scan, v)))
+    return float((si.batch([c["view_ids"] for c in cams]).cpu() - want).abs().max())
 
 
 def ingest_bench(a, calls=20, blocks=5):
@@ -130,6 +250,8 @@ def main():
     ap.add_argument("--views", type=int, default=11)
     ap.add_argument("--H", type=int, default=1184)
     ap.add_argument("--W", type=int, default=1600)
+    ap.add_argument("--H0", type=int, default=None, help="height of the image files (default: --H, no resize)")
+    ap.add_argument("--W0", type=int, default=None, help="width of the image files (default: --W)")
     ap.add_argument("--nviews", type=int, default=5, help="views per forward (reference + sources)")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--repeats", type=int, default=5)
@@ -143,31 +265,49 @@ def main():
     root = tempfile.mkdtemp(prefix="bench_scene_", dir=a.tmp)
     try:
         data, scan = os.path.join(root, "data"), "scan1"
-        write_scene(data, scan, a.H, a.W, a.views)
-        print("scene written: %d views at %d x %d" % (a.views, a.H, a.W), flush=True)
-        times, counts = {"files": [], "memory": []}, {}
+        H0, W0 = a.H0 or a.H, a.W0 or a.W
+        write_scene(data, scan, H0, W0, a.views)
+        from damvsnet_amd import mvsio
+        new_w, new_h, _ = mvsio.scale_mvs_camera(H0, W0, np.eye(3, dtype=np.float32), a.W, a.H)
+        resized = (new_h, new_w) != (H0, W0)
+        print("scene written: %d views at %d x %d, working size %d x %d" % (a.views, H0, W0, new_h, new_w), flush=True)
+        names = ("files", "memory", "device")
+        times, counts = {k: [] for k in names}, {}
+        read = lambda name: open(os.path.join(root, name + ".ply"), "rb").read()
         for rep in range(a.repeats + 1):  # run 0 is the warm-up of each
-            for name in (("files", "memory") if rep % 2 == 0 else ("memory", "files")):
+            for name in names[rep % 3:] + names[:rep % 3]:
                 out_dir, ply = os.path.join(root, "out_" + name), os.path.join(root, name + ".ply")
                 shutil.rmtree(out_dir, ignore_errors=True)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                n = file_path(net, data, scan, out_dir, ply, a) if name == "files" else memory_path(net, data, scan, ply, a)
+                if name == "files":
+                    n = file_path(net, data, scan, out_dir, ply, a)
+                else:
+                    n = memory_path(net, data, scan, ply, a, "host" if name == "memory" else "device")
                 dt = time.perf_counter() - t0
                 counts[name] = n
                 if rep:
                     times[name].append(round(dt, 3))
                 print("run %d %-6s %.3f s, %d points%s" % (rep, name, dt, n, "" if rep else " (warm-up)"), flush=True)
-            same = open(os.path.join(root, "files.ply"), "rb").read() == open(os.path.join(root, "memory.ply"), "rb").read()
-            assert same and counts["files"] == counts["memory"], "the two paths wrote different clouds"
+            assert read("files") == read("memory") and counts["files"] == counts["memory"], \
+                "the file path and the memory path wrote different clouds"
+            assert resized or (read("device") == read("memory") and counts["device"] == counts["memory"]), \
+                "the device inputs and the host inputs wrote different clouds"
+        imgs_diff = first_batch_imgs_diff(data, scan, a) if resized else 0.0
+        assert imgs_diff <= 2.0 ** -21, "imgs of the device inputs differ from the host's by %.3e" % imgs_diff
         med = {k: float(np.median(v)) for k, v in times.items()}
-        res = {"metric": "seconds, loaded model to PLY on disk", "views": a.views, "shape": [a.H, a.W],
-               "nviews": a.nviews, "batch": a.batch, "dtype": "bf16", "ndepths": [48, 32, 8], "points": counts["memory"],
-               "ply_identical": True, "files_s": times["files"], "memory_s": times["memory"],
-               "files_median_s": round(med["files"], 3), "memory_median_s": round(med["memory"], 3),
-               "files_spread_s": [min(times["files"]), max(times["files"])],
-               "memory_spread_s": [min(times["memory"]), max(times["memory"])],
-               "ratio_memory_over_files": round(med["memory"] / med["files"], 4), "ingest": ingest_bench(a)}
+        res = {"metric": "seconds, loaded model to PLY on disk", "views": a.views, "image_files": [H0, W0],
+               "shape": [new_h, new_w], "nviews": a.nviews, "batch": a.batch, "dtype": "bf16", "ndepths": [48, 32, 8],
+               "points": counts, "ply_identical": {"files_memory": True, "device_memory": not resized},
+               "imgs_max_diff_device_host": imgs_diff}
+        for k in names:
+            res[k + "_s"], res[k + "_median_s"] = times[k], round(med[k], 3)
+            res[k + "_spread_s"] = [min(times[k]), max(times[k])]
+        res["ratio_memory_over_files"] = round(med["memory"] / med["files"], 4)
+        res["ratio_device_over_memory"] = round(med["device"] / med["memory"], 4)
+        res["memory_breakdown_s"] = breakdown(net, data, scan, os.path.join(root, "breakdown.ply"), a)
+        res["ingest"] = ingest_bench(argparse.Namespace(**dict(vars(a), H=new_h, W=new_w)))
+        res["inputs"] = inputs_bench(a)
     finally:
         shutil.rmtree(root, ignore_errors=True)
     line = json.dumps(res)
