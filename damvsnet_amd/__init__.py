@@ -5,7 +5,7 @@ Heavy imports (torch modules, the HIP library) are lazy so that ``damvsnet_amd.s
 """
 
 __all__ = ["CascadeMVSNet", "DepthNet", "homo_warping", "load_library", "SceneMaps", "SceneInputs",
-           "reconstruct_scene"]
+           "SceneFeatures", "reconstruct_scene"]
 
 
 def __getattr__(name):
@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ("DepthNet", "homo_warping"):
         from . import depthnet
         return getattr(depthnet, name)
-    if name in ("SceneMaps", "SceneInputs", "reconstruct_scene"):
+    if name in ("SceneMaps", "SceneInputs", "SceneFeatures", "reconstruct_scene"):
         from . import scene
         return getattr(scene, name)
     if name == "load_library":

@@ -48,6 +48,7 @@ class DamvsConv2dDesc(ctypes.Structure):
 FUSION_MAX_SRC = 10
 SCENE_MAX_BATCH = 64
 INPUTS_MAX_IMAGES = 128
+FEATURES_MAX_PAIRS, FEATURES_MAX_TENSORS = 128, 4
 _f = ctypes.c_float
 
 
@@ -125,6 +126,9 @@ SIGNATURES = (
                                    c_void_p, ctypes.c_longlong, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p)),
     ("damvs_scene_inputs", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int),
                                    c_void_p)),
+    ("damvs_feature_gather", c_int, (c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p),
+                                     ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(c_int),
+                                     ctypes.POINTER(c_void_p))),
     ("damvs_conv2d_border_bias", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                          ctypes.POINTER(ctypes.c_float), c_void_p)),
 )

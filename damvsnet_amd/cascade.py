@@ -111,6 +111,30 @@ class CascadeMVSNet(nn.Module):
         f = feat(x)
         return [{k: v.reshape(B, N, *v.shape[1:])[:, i] for k, v in f.items()} for i in range(N)]
 
+    def _given_features(self, features, imgs, proj_matrices):
+        """forward's ``features``: the list extract_features returns (scene.SceneFeatures.batch), checked against the
+        batch it is to serve. ValueError before any device work."""
+        if self.frontend_impl != "hip":
+            raise ValueError("features= takes the HIP front-end's NHWC features (frontend_impl=\"hip\")")
+        B, H, W = imgs.shape[0], imgs.shape[3], imgs.shape[4]
+        features = list(features)
+        fd = self.frontend_dtype or torch.float32
+        for s in range(self.num_stage):
+            name = "stage%d" % (s + 1)
+            if len(features) != proj_matrices[name].shape[1]:
+                raise ValueError("features of %d views, proj_matrices[\"%s\"] of %d" % (
+                    len(features), name, proj_matrices[name].shape[1]))
+            scale = int(STAGE_SCALE[name])
+            want = (B, H // scale, W // scale, self.feature.out_channels[s])
+            for n, f in enumerate(features):
+                t = f.get(name) if isinstance(f, dict) else None
+                if not torch.is_tensor(t) or tuple(t.shape) != want or t.dtype != fd or t.device != imgs.device \
+                        or not t.is_contiguous():
+                    raise ValueError("features[%d][\"%s\"] must be a contiguous %s tensor %s on %s (got %s)" % (
+                        n, name, fd, want, imgs.device,
+                        "%s %s on %s" % (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t).__name__))
+        return features
+
     def _side_streams(self, n, device):
         """The sub-batch streams, one process-wide set per device shared by every model: torch.cuda.Stream() hands out
         the next stream of PyTorch's pool, and HIP places streams on its hardware queues in creation order, so a second
@@ -124,7 +148,7 @@ class CascadeMVSNet(nn.Module):
         return pool[:n]
 
     def _forward_streams(self, imgs, proj_matrices, depth_values, intrinsics_matrices, nstreams, check_range=True,
-                         offset=None):
+                         offset=None, features=None):
         """The batch as ``nstreams`` sub-batches of reference views on concurrent HIP streams, merged along the
         batch. Per sample every kernel sees the same inputs as in one batch, so the outputs are bitwise those of
         the single-stream forward (tests/test_gpu_streams.py); the gain is overlap between kernels with different
@@ -138,6 +162,8 @@ class CascadeMVSNet(nn.Module):
         def part(x, a, b):
             if isinstance(x, dict):
                 return {k: part(v, a, b) for k, v in x.items()}
+            if isinstance(x, list):  # the given features: one dict per view
+                return [part(v, a, b) for v in x]
             return x[a:b] if isinstance(x, torch.Tensor) else x
 
         pool = self._side_streams(nstreams, imgs.device)
@@ -157,7 +183,7 @@ class CascadeMVSNet(nn.Module):
             with torch.cuda.stream(st):
                 outs.append(self.forward(part(imgs, a, b), part(proj_matrices, a, b), part(depth_values, a, b),
                                          part(intrinsics_matrices, a, b), check_range=False,
-                                         stage_hook=hook if offset else None))
+                                         stage_hook=hook if offset else None, features=part(features, a, b)))
             gate = mark.get("ev")
 
         # batch-sized outputs allocated on the main stream, each stream copying its rows right after its own
@@ -195,7 +221,7 @@ class CascadeMVSNet(nn.Module):
         return full
 
     def forward(self, imgs, proj_matrices, depth_values, intrinsics_matrices=None, stage_hook=None, depthnet=None,
-                streams=1, check_range=True, stream_offset="auto"):
+                streams=1, check_range=True, stream_offset="auto", features=None):
         """``depthnet``: optional stage runner (stage_idx, NHWC features, proj, hyps, cost_regularization) -> dict,
         e.g. sharded.DepthShardedDepthNet (one depth map over several GPUs); default: this model's DepthNet.
         ``streams`` > 1 runs the batch as that many sub-batches on concurrent streams (_forward_streams; not with
@@ -205,13 +231,19 @@ class CascadeMVSNet(nn.Module):
         status (damvs_stage_status, one host sync per forward) and raise damvsnet_amd._capi.DamvsRangeError if any
         depth / confidence / variance is non-finite. With a custom ``depthnet`` runner the range status is that
         runner's business: sharded.DepthShardedDepthNet runs the stage as split layer calls, which do not write a
-        status word, so no DamvsRangeError is raised on that path."""
+        status word, so no DamvsRangeError is raised on that path.
+        ``features``: what extract_features(imgs) would return, computed elsewhere (scene.SceneFeatures.batch serves a
+        scan's views from one FeatureNet pass each): FeatureNet is not run, the view count is len(features), and
+        ``imgs`` may carry the reference view alone, (B, 1, 3, H, W): only imgs[:, 0] is read. HIP front-end only;
+        ValueError if the features do not fit the batch (view count against proj_matrices, B, sizes, dtype)."""
+        if features is not None:
+            features = self._given_features(features, imgs, proj_matrices)
         if streams > 1 and imgs.shape[0] > 1 and stage_hook is None and depthnet is None and imgs.is_cuda \
                 and not self.refine:
             if stream_offset == "auto":
                 stream_offset = "stage1.hypotheses" if self.compute_dtype == torch.float32 else None
             return self._forward_streams(imgs, proj_matrices, depth_values, intrinsics_matrices,
-                                         min(int(streams), imgs.shape[0]), check_range, stream_offset)
+                                         min(int(streams), imgs.shape[0]), check_range, stream_offset, features)
         if self.refine:
             raise NotImplementedError("refine=True: the reference RefineNet forward is not runnable "
                                       "(models/module.py:602 calls F.cat)")
@@ -220,7 +252,8 @@ class CascadeMVSNet(nn.Module):
         hook = stage_hook or (lambda name: None)
         B, N, _, H, W = imgs.shape
         hook("features")
-        features = self.extract_features(imgs)
+        if features is None:
+            features = self.extract_features(imgs)
         outputs = {}
         depth = exp_var = conf = None
         for s in range(self.num_stage):

@@ -292,14 +292,15 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #define DAMVS_BUILD_ID "unstamped"
 #endif
 // The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so,
-// libdamvs_inputs.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
+// libdamvs_inputs.so, libdamvs_features.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
   static const std::string id = [] {
     std::string s(DAMVS_BUILD_ID);
     const std::pair<const char*, const char*> side[] = {{"libdamvs_fusion.so", fusion_static_build_id()},
                                                         {"libdamvs_cloud.so", fusion_cloud_build_id()},
                                                         {"libdamvs_scene.so", scene_build_id()},
-                                                        {"libdamvs_inputs.so", inputs_build_id()}};
+                                                        {"libdamvs_inputs.so", inputs_build_id()},
+                                                        {"libdamvs_features.so", features_build_id()}};
     for (const auto& l : side)
       if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
     return s;
@@ -1046,6 +1047,46 @@ int damvs_scene_inputs(void* stream, int n_images, int H0, int W0, int H, int W,
   a.rgb_store = rgb_store;
   a.out = out;
   return hip_check(launch_scene_inputs(static_cast<hipStream_t>(stream), n_images, a), "scene_inputs launch");
+}
+
+// ============================================================================ scene features
+int damvs_feature_gather(void* stream, int n_pairs, int K, int V, const void* const* stores,
+                         const unsigned long long* view_bytes, const int* slots, void* const* outs) {
+  if (!stores) return fail(DAMVS_E_ARG, "null stores");
+  if (!view_bytes) return fail(DAMVS_E_ARG, "null view_bytes");
+  if (!slots) return fail(DAMVS_E_ARG, "null slots");
+  if (!outs) return fail(DAMVS_E_ARG, "null outs");
+  if (n_pairs < 1 || n_pairs > kFeaturesMaxPairs)
+    return fail(DAMVS_E_SHAPE, "n_pairs %d not in [1, %d]", n_pairs, kFeaturesMaxPairs);
+  if (K < 1 || K > kFeaturesMaxTensors) return fail(DAMVS_E_SHAPE, "K %d not in [1, %d]", K, kFeaturesMaxTensors);
+  if (V < 1) return fail(DAMVS_E_SHAPE, "V %d < 1", V);
+  FeaturesArgs a;
+  for (int k = 0; k < kFeaturesMaxTensors; ++k) {
+    a.store[k] = nullptr;
+    a.out[k] = nullptr;
+    a.nvec[k] = 0;
+  }
+  for (int k = 0; k < K; ++k) {
+    if (!stores[k]) return fail(DAMVS_E_ARG, "null stores[%d]", k);
+    if (!outs[k]) return fail(DAMVS_E_ARG, "null outs[%d]", k);
+    // the kernel moves 16-byte vectors
+    if (reinterpret_cast<uintptr_t>(stores[k]) & 15) return fail(DAMVS_E_ARG, "stores[%d] is not 16-byte aligned", k);
+    if (reinterpret_cast<uintptr_t>(outs[k]) & 15) return fail(DAMVS_E_ARG, "outs[%d] is not 16-byte aligned", k);
+    const unsigned long long vb = view_bytes[k];
+    if (vb == 0) return fail(DAMVS_E_SHAPE, "view_bytes[%d] is 0", k);
+    if (vb % 16) return fail(DAMVS_E_SHAPE, "view_bytes[%d] %llu is not a multiple of 16", k, vb);
+    // the offsets within a view are 32-bit
+    if (vb >= (1ull << 31)) return fail(DAMVS_E_SHAPE, "view_bytes[%d] %llu >= 2^31", k, vb);
+    a.store[k] = static_cast<const unsigned char*>(stores[k]);
+    a.out[k] = static_cast<unsigned char*>(outs[k]);
+    a.nvec[k] = (unsigned)(vb / 16);
+  }
+  for (int i = 0; i < n_pairs; ++i) {
+    if (slots[i] < 0 || slots[i] >= V) return fail(DAMVS_E_SHAPE, "slot %d of pair %d outside [0, %d)", slots[i], i, V);
+    a.slots[i] = slots[i];
+  }
+  for (int i = n_pairs; i < kFeaturesMaxPairs; ++i) a.slots[i] = 0;
+  return hip_check(launch_feature_gather(static_cast<hipStream_t>(stream), n_pairs, K, a), "feature_gather launch");
 }
 
 }  // extern "C"

@@ -238,6 +238,22 @@ struct InputsArgs {
 hipError_t launch_scene_inputs(hipStream_t s, int n_images, const InputsArgs& a);
 const char* inputs_build_id();
 
+// ---------------------------------------------------------------- scene features (k_features.hip, libdamvs_features.so)
+constexpr int kFeaturesMaxPairs = 128;      // DAMVS_FEATURES_MAX_PAIRS: the slot table lives in the kernel arguments
+constexpr int kFeaturesMaxTensors = 4;      // DAMVS_FEATURES_MAX_TENSORS
+constexpr int kFeaturesBlock = 256;         // threads, one 16-byte vector each per grid pass
+constexpr int kFeaturesGridBlocks = 2048;   // the launch's blocks over all pairs and tensors (256 CUs x 8), about
+struct FeaturesArgs {
+  const unsigned char* store[kFeaturesMaxTensors];  // [V][view_bytes[k]], 16-byte aligned
+  unsigned char* out[kFeaturesMaxTensors];          // [n_pairs][view_bytes[k]], 16-byte aligned
+  unsigned nvec[kFeaturesMaxTensors];               // view_bytes[k] / 16, in [1, 2^27)
+  int slots[kFeaturesMaxPairs];                     // pair i -> slot
+};
+// blocks along x: those the largest tensor needs, at most kFeaturesGridBlocks / (n_pairs * K) (at least 1)
+unsigned feature_gather_grid_x(int n_pairs, int K, unsigned max_nvec);
+hipError_t launch_feature_gather(hipStream_t s, int n_pairs, int K, const FeaturesArgs& a);
+const char* features_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -235,17 +235,23 @@ class HipFeatureNet:
     # full-resolution 8-channel ones, so view groups are sized to keep those under this bound
     MAX_ACT_BYTES = 3 << 29  # 1.5 GiB
 
-    def __call__(self, x):
+    def __call__(self, x, out=None):
         """x: (B, 3, H, W), or (B, N, 3, H, W) views batched view-major (row v*B + b) with no copy of the
         images: the first layer reads each view's planes in place, one launch per view. Views run in groups when one
         batch of all of them would pass the 32-bit offset bound (cfgE's 11 views x B=4 at 1920 x 1056 in fp32: 2.85 GB per
-        8-channel activation); the groups' outputs are concatenated in view order."""
+        8-channel activation); the groups' outputs are concatenated in view order.
+        out: optional {stage: preallocated output}, contiguous tensors of the outputs' shapes and dtype (slices of a
+        scene store, scene.SceneFeatures): the last layer of each output writes there and those tensors are returned."""
         if x.dim() == 5:
             Bv, N, _, H, W = x.shape
             es = torch.tensor([], dtype=self.c0[0].dtype).element_size()
             per_view = Bv * H * W * 8 * es
             if N > 1 and N * per_view > self.MAX_ACT_BYTES:
                 g = max(1, self.MAX_ACT_BYTES // per_view)
+                if out is not None:  # the groups write their rows of the given outputs
+                    for v in range(0, N, g):
+                        self(x[:, v:v + g], out={k: t[v * Bv:(v + g) * Bv] for k, t in out.items()})
+                    return dict(out)
                 parts = [self(x[:, v:v + g]) for v in range(0, N, g)]
                 return {k: torch.cat([p[k] for p in parts], 0) for k in parts[0]}
             B = N * Bv
@@ -265,10 +271,11 @@ class HipFeatureNet:
         for L in self.c2:
             t = L(B, t.shape[1], t.shape[2], t)
         c2 = t
-        out = {"stage1": self.out1(B, c2.shape[1], c2.shape[2], c2)}
+        given = out if out is not None else {}
+        out = {"stage1": self.out1(B, c2.shape[1], c2.shape[2], c2, out=given.get("stage1"))}
         if self.arch == "fpn":
             f = self.inner1(B, c1.shape[1], c1.shape[2], c1, res_post=c2, post_up=2)
-            out["stage2"] = self.out2(B, f.shape[1], f.shape[2], f)
+            out["stage2"] = self.out2(B, f.shape[1], f.shape[2], f, out=given.get("stage2"))
             if self.num_stage == 3:
                 # out3(up2(f) + inner2(c0)) without the 32-channel full-resolution sum (fpn_top_layers)
                 lib = self.top_c0._lib
@@ -276,7 +283,13 @@ class HipFeatureNet:
                     ap, bc, ws = self.top_fused
                     if ap.device != c0.device:
                         self.top_fused = ap, bc, ws = ap.to(c0.device), bc.to(c0.device), ws
-                    o3 = torch.empty(B, h, w, 8, device=c0.device, dtype=c0.dtype)
+                    o3 = given.get("stage3")
+                    if o3 is None:
+                        o3 = torch.empty(B, h, w, 8, device=c0.device, dtype=c0.dtype)
+                    elif tuple(o3.shape) != (B, h, w, 8) or o3.dtype != c0.dtype or not o3.is_contiguous() \
+                            or o3.device != c0.device:
+                        raise ValueError("FeatureNet out[\"stage3\"]: need a contiguous %s %s tensor on %s, got %s %s"
+                                         % (c0.dtype, (B, h, w, 8), c0.device, o3.dtype, tuple(o3.shape)))
                     if ws is None:
                         check(lib.damvs_fpn_top_forward(_capi.stream_ptr(c0.device), B, h, w, ptr(c0), ptr(f), ptr(ap),
                                                         ptr(bc), ptr(o3)))
@@ -285,7 +298,7 @@ class HipFeatureNet:
                                                             ptr(ap), ws, ptr(bc), ptr(o3)))
                 else:
                     t = self.top_up(B, f.shape[1], f.shape[2], f)
-                    o3 = self.top_c0(B, h, w, c0, res_pre=t)
+                    o3 = self.top_c0(B, h, w, c0, res_pre=t, out=given.get("stage3"))
                 check(lib.damvs_conv2d_border_bias(_capi.stream_ptr(o3.device), DTYPES[o3.dtype], B, h, w, o3.shape[3],
                                                    self.top_c0.cout, _capi.float_ptr(self.top_corr), ptr(o3)))
                 out["stage3"] = o3
@@ -297,7 +310,7 @@ class HipFeatureNet:
             f = conv(B, y.shape[1], y.shape[2], y, skip)
             key = "stage%d" % (i + 2)
             L = self.out2 if i == 0 else self.out3
-            out[key] = L(B, f.shape[1], f.shape[2], f)
+            out[key] = L(B, f.shape[1], f.shape[2], f, out=given.get(key))
         return out
 
 

@@ -14,6 +14,11 @@ The other end of the forward (row f3): `SceneInputs` keeps the scan's decoded im
 uploaded once, and writes the forward's `imgs` for a batch by one HIP launch (k_inputs.hip, damvs_scene_inputs) in
 place of the host's float conversion, resize, stack and per-batch float32 upload (`reconstruct_scene(inputs="device")`).
 
+Between the two (row f1): FeatureNet's output depends on the image alone, and a scan lists each view in about `nviews`
+samples. `SceneFeatures` runs FeatureNet once per view into scene-resident stores and hands a batch the list
+`CascadeMVSNet.extract_features` would compute, by one HIP launch that gathers the views' blocks (k_features.hip,
+damvs_feature_gather); `CascadeMVSNet.forward(features=...)` takes it (`reconstruct_scene(features="scene")`).
+
 A stated difference: the reference re-encodes the reference image as JPEG (test_uni.py:286-287) and the fusion reads
 that file back, so its colours carry JPEG loss. The in-memory path takes the colour before the JPEG. Positions, masks
 and point order are those of the file path bit for bit; colours are equal whenever the file path's images are lossless.
@@ -256,10 +261,133 @@ class SceneInputs:
         return imgs
 
 
-def _device_batches(ds, scan, batch, device, decode_workers):
-    """reconstruct_scene's inputs="device": every view of the scan decoded in `decode_workers` threads and put into a
-    SceneInputs as soon as it is ready, then per batch of `batch` samples (the samples without pixels, `imgs` in one
-    reused buffer)."""
+class SceneFeatures:
+    """FeatureNet's outputs for a scene's views, each computed once: `stores["stage1" | "stage2" | "stage3"]`, one
+    tensor (V, h_s, w_s, C_s) per FeatureNet output at (H/4, W/4, 32), (H/2, W/2, 16), (H, W, 8) in the HIP front
+    end's storage dtype (`model.frontend_dtype` or float32), NHWC, exactly what `model.extract_features` returns; view
+    i of `view_ids` in slot i. `put` runs FeatureNet over a group of images into their slots; `batch` is one launch of
+    damvs_feature_gather (k_features.hip) that copies the listed views' blocks into the per-view tensors a stage takes.
+    The stores hold 14 * H * W elements per view: about 53 MB per view at 1184 x 1600 in bf16 and 106 MB in fp32
+    (`nbytes` reports the total; 49 views: 2.6 GB / 5.2 GB). The caller decides whether a scan fits.
+    HIP front end only. The features belong to the weights they were computed with: after the model's weights changed
+    (or the model moved), the next `put` or `batch` raises ValueError."""
+
+    STAGES = ("stage1", "stage2", "stage3")
+
+    def __init__(self, model, view_ids, H, W, device="cuda"):
+        view_ids = [int(v) for v in view_ids]
+        if len(set(view_ids)) != len(view_ids) or not view_ids:
+            raise ValueError("view_ids must be a non-empty list of distinct view ids")
+        if getattr(model, "frontend_impl", None) != "hip":
+            raise ValueError("SceneFeatures keeps the HIP front end's NHWC features (frontend_impl=\"hip\")")
+        if H < 4 or W < 4 or H % 4 or W % 4:
+            raise ValueError("H and W must be positive multiples of 4 (got %d x %d)" % (H, W))
+        self.model, self.view_ids, self.H, self.W, self.device = model, view_ids, int(H), int(W), torch.device(device)
+        self.slot = {v: i for i, v in enumerate(view_ids)}
+        self.dtype = model.frontend_dtype or torch.float32
+        self.stores = {}
+        for name, scale, C in zip(self.STAGES, (4, 2, 1), model.feature.out_channels):
+            self.stores[name] = torch.empty(len(view_ids), self.H // scale, self.W // scale, (C + 3) // 4 * 4,
+                                            device=self.device, dtype=self.dtype)
+        self.nbytes = sum(t.numel() * t.element_size() for t in self.stores.values())
+        self._put, self._key = set(), None
+
+    def _featurenet(self):
+        """The model's HipFeatureNet; ValueError if views were put under other weights (CascadeMVSNet._folded_key)."""
+        feat, _ = self.model._frontend()
+        key = self.model._folded_key
+        if self._put and key != self._key:
+            raise ValueError("the model's weights changed after views %s were put: their features are stale" %
+                             sorted(self._put))
+        self._key = key
+        return feat
+
+    def put(self, view_ids, imgs):
+        """view_ids: G views; imgs: their (G, 3, H, W) float32 planar images on the device, what the forward takes.
+        One batched FeatureNet call on the current stream, no host synchronisation (groups that would pass
+        HipFeatureNet.MAX_ACT_BYTES are split). The last layer of each output writes into the stores when the group's
+        slots are consecutive; otherwise the outputs are copied into their slots (index_copy_).
+        ValueError, naming the views, before anything is written: an unknown view, a view put twice, imgs of another
+        shape, dtype or device."""
+        view_ids = [int(v) for v in view_ids]
+        for v in view_ids:
+            if v not in self.slot:
+                raise ValueError("view %d is not one of the scene's views %s" % (v, self.view_ids))
+            if v in self._put or view_ids.count(v) > 1:
+                raise ValueError("view %d put twice" % v)
+        G, want = len(view_ids), (len(view_ids), 3, self.H, self.W)
+        store = self.stores["stage3"]
+        if not torch.is_tensor(imgs) or imgs.dtype != torch.float32 or tuple(imgs.shape) != want or \
+                imgs.device != store.device:
+            raise ValueError("imgs of views %s must be a float32 tensor %s on %s (got %s)" % (
+                view_ids, want, store.device,
+                "%s %s on %s" % (imgs.dtype, tuple(imgs.shape), imgs.device) if torch.is_tensor(imgs)
+                else type(imgs).__name__))
+        if not G:
+            return
+        feat = self._featurenet()
+        per_image = self.H * self.W * 8 * store.element_size()  # FeatureNet's widest activation
+        g = max(1, feat.MAX_ACT_BYTES // per_image)
+        slots = [self.slot[v] for v in view_ids]
+        with torch.no_grad():
+            for i0 in range(0, G, g):
+                sl, x = slots[i0:i0 + g], imgs[i0:i0 + g]
+                if sl == list(range(sl[0], sl[0] + len(sl))):
+                    feat(x, out={k: t[sl[0]:sl[0] + len(sl)] for k, t in self.stores.items()})
+                else:
+                    f = feat(x)
+                    index = torch.tensor(sl, dtype=torch.int64).to(store.device, non_blocking=True)
+                    for k, t in self.stores.items():
+                        t.index_copy_(0, index, f[k])
+        self._put.update(view_ids)
+
+    def buffers(self, n_pairs):
+        """{stage: (n_pairs, h_s, w_s, C_s)} uninitialised, for `batch(out=)`."""
+        return {k: torch.empty((n_pairs,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+                for k, t in self.stores.items()}
+
+    def batch(self, views, out=None):
+        """views: B lists of N view ids, the reference view first (a view may repeat inside a sample: pair.txt's fill
+        rule) -> the list `extract_features` returns for those images: N dicts {stage: (B, h_s, w_s, C_s)}, view n's
+        tensors contiguous slices (rows n * B .. (n + 1) * B) of one buffer per stage, written by one
+        damvs_feature_gather launch on the current stream, pairs ordered view-major. No allocation when `out` fits:
+        {stage: buffer} as `buffers` returns (contiguous, the stores' dtype and device, at least B * N views' elements),
+        whose leading parts are used; otherwise new buffers. ValueError, naming the views: a view that was never put,
+        lists of different lengths, B * N outside 1..DAMVS_FEATURES_MAX_PAIRS."""
+        views = [[int(v) for v in sample] for sample in views]
+        B, N = len(views), len(views[0]) if views else 0
+        if any(len(sample) != N for sample in views):
+            raise ValueError("ragged view lists %s: every sample needs the same number of views" % views)
+        n = B * N
+        if not 1 <= n <= _capi.FEATURES_MAX_PAIRS:
+            raise ValueError("a batch of 1..%d (sample, view) pairs per call (got %d x %d, views %s)" % (
+                _capi.FEATURES_MAX_PAIRS, B, N, views))
+        for v in (v for sample in views for v in sample):
+            if v not in self._put:
+                raise ValueError("view %d was never put" % v)
+        self._featurenet()
+        bufs = {}
+        for k, t in self.stores.items():
+            shape, o = (n,) + tuple(t.shape[1:]), out.get(k) if isinstance(out, dict) else None
+            need = n * t[0].numel()
+            fits = torch.is_tensor(o) and o.dtype == t.dtype and o.device == t.device and o.is_contiguous() and \
+                o.numel() >= need
+            bufs[k] = o.view(-1)[:need].view(shape) if fits else torch.empty(shape, device=t.device, dtype=t.dtype)
+        K = len(self.STAGES)
+        stores = (ctypes.c_void_p * K)(*[self.stores[k].data_ptr() for k in self.STAGES])
+        outs = (ctypes.c_void_p * K)(*[bufs[k].data_ptr() for k in self.STAGES])
+        view_bytes = (ctypes.c_ulonglong * K)(*[self.stores[k][0].numel() * self.stores[k].element_size()
+                                                 for k in self.STAGES])
+        slots = (ctypes.c_int * n)(*[self.slot[views[b][v]] for v in range(N) for b in range(B)])
+        lib = _capi.load_library()
+        check(lib.damvs_feature_gather(_capi.stream_ptr(self.stores["stage3"].device), n, K, len(self.view_ids), stores,
+                                       view_bytes, slots, outs))
+        return [{k: bufs[k][v * B:(v + 1) * B] for k in self.STAGES} for v in range(N)]
+
+
+def _device_store(ds, scan, device, decode_workers):
+    """reconstruct_scene's inputs="device": the samples without pixels and a SceneInputs with every view of the scan,
+    decoded in `decode_workers` threads and put as soon as it is ready."""
     samples = [ds.cameras(i) for i in range(len(ds))]
     sizes = sorted({s["original_size"] for s in samples})
     if len(sizes) != 1:
@@ -270,16 +398,25 @@ def _device_batches(ds, scan, batch, device, decode_workers):
         decoding = {pool.submit(mvsio.read_img_bytes, ds._img_path(scan, v)): v for v in store.view_ids}
         for done in cf.as_completed(decoding):
             store.put(decoding[done], done.result())
-    reused = None
+    return samples, store
+
+
+def _device_batches(samples, store, batch, reference_only=False, reused=None):
+    """Per batch of `batch` samples (the samples, `imgs` in one reused buffer); reference_only: `imgs` holds view 0 of
+    each sample alone, (B, 1, 3, H, W)."""
     for i0 in range(0, len(samples), batch):
         items = samples[i0:i0 + batch]
-        imgs = store.batch([it["view_ids"] for it in items], out=reused)
+        imgs = store.batch([it["view_ids"][:1] if reference_only else it["view_ids"] for it in items], out=reused)
         reused = imgs if reused is None else reused  # the first batch is the largest
         yield items, imgs
 
 
+def _groups(views, n):
+    return [views[i:i + n] for i in range(0, len(views), n)]
+
+
 def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192, interval_scale=1.06, max_h=1184,
-                      max_w=1600, batch=4, streams=1, inputs="host", decode_workers=4, **fuse_kwargs):
+                      max_w=1600, batch=4, streams=1, inputs="host", decode_workers=4, features="batch", **fuse_kwargs):
     """One scan from its directory (<datapath>/<scan>/{pair.txt, cams/, images/}) to a fused PLY without the disk in
     between: mvsio.EvalScenes samples in batches of `batch` reference views through `model` (a CascadeMVSNet on a HIP
     device; `streams` as in its forward) with check_range=False, each batch into a SceneMaps, one
@@ -292,20 +429,57 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
     soon as it is decoded and lets one launch per batch write `imgs` into one reused buffer; the cameras come from
     EvalScenes.cameras. The two agree bit for bit when the images need no resize; a resized image differs from the
     host's in its last bits (at most 2^-21: tests/test_inputs.py), so the depth maps may too. The device path needs
-    image files of one size and raises ValueError otherwise."""
+    image files of one size and raises ValueError otherwise.
+    features: "batch" runs FeatureNet on the B * nviews images of every batch. "scene" first puts every view that a
+    sample lists through FeatureNet once, in groups of at most batch * nviews images, into a SceneFeatures (its
+    docstring states the memory: 14 * H * W elements per view); each batch then uploads or writes its reference views'
+    images alone, gathers its features by one launch and calls model(..., features=...). The maps and the PLY are those
+    of "batch" bit for bit (FeatureNet's result for an image does not depend on the rest of its batch)."""
     if inputs not in ("host", "device"):
         raise ValueError("inputs must be \"host\" or \"device\" (got %r)" % (inputs,))
+    if features not in ("batch", "scene"):
+        raise ValueError("features must be \"batch\" or \"scene\" (got %r)" % (features,))
     if not isinstance(decode_workers, int) or decode_workers < 1:
         raise ValueError("decode_workers must be a positive integer (got %r)" % (decode_workers,))
     ds = mvsio.EvalScenes(datapath, [scan], nviews, ndepths=ndepths, interval_scale=interval_scale, max_h=max_h,
                           max_w=max_w, cache_views=True)
     device = next(model.parameters()).device
     refs = [ref for _, ref, _ in ds.metas]
-    maps = None
-    device_batches = _device_batches(ds, scan, batch, device, decode_workers) if inputs == "device" else None
+    maps = feats = fbufs = None
+    device_batches = None
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    sample_views = lambda i: [ds.metas[i][1]] + ds.metas[i][2][:nviews - 1]
     with torch.no_grad():
+        if inputs == "device":
+            samples, store = _device_store(ds, scan, device, decode_workers)
+            reused = None
+            if features == "scene":
+                feats = SceneFeatures(model, store.view_ids, store.H, store.W, device)
+                for group in _groups(store.view_ids, batch * nviews):
+                    imgs = store.batch([[v] for v in group], out=reused)
+                    reused = imgs if reused is None else reused  # the first group is the largest
+                    feats.put(group, imgs[:, 0])
+            device_batches = _device_batches(samples, store, batch, features == "scene", reused)
+        elif features == "scene":
+            used = sorted({v for i in range(len(ds)) for v in sample_views(i)})
+            found = {}  # view -> its scaled host image, until its group is put
+            for i in range(len(ds)):
+                it = ds[i]
+                if feats is None:
+                    feats = SceneFeatures(model, used, it["imgs"].shape[2], it["imgs"].shape[3], device)
+                if it["imgs"].shape[2:] != (feats.H, feats.W):
+                    raise ValueError("view %d of %s comes out at %s, the scene at %s: one scene, one size" % (
+                        refs[i], scan, it["imgs"].shape[2:], (feats.H, feats.W)))
+                for n, v in enumerate(sample_views(i)):
+                    if v not in found and v not in feats._put:
+                        found[v] = it["imgs"][n]
+                if len(found) >= batch * nviews or i == len(ds) - 1:
+                    for group in _groups(sorted(found), batch * nviews):
+                        feats.put(group, up(np.stack([found[v] for v in group])))
+                    found = {}
+        if feats is not None:
+            fbufs = feats.buffers(min(batch, len(ds)) * nviews)
         for i0 in range(0, len(ds), batch):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
             if device_batches is not None:
                 items, imgs = next(device_batches)
             else:
@@ -314,7 +488,7 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
                 if len(shapes) != 1 or (maps is not None and next(iter(shapes))[2:] != (maps.H, maps.W)):
                     raise ValueError("views %s of %s come out at sizes %s: one scene, one size" % (
                         refs[i0:i0 + len(items)], scan, sorted(shapes)))
-                imgs = up(np.stack([it["imgs"] for it in items]))
+                imgs = up(np.stack([it["imgs"][:1] if feats is not None else it["imgs"] for it in items]))
             proj_host = {k: np.stack([it["proj_matrices"][k] for it in items]) for k in items[0]["proj_matrices"]}
             proj = {k: up(v) for k, v in proj_host.items()}
             depth_values = up(np.stack([it["depth_values"] for it in items]))
@@ -322,7 +496,11 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
                    for k in items[0]["intrinsics_matrices"]}
             if maps is None:
                 maps = SceneMaps(refs, imgs.shape[3], imgs.shape[4], device)
-            out = model(imgs, proj, depth_values, ins, streams=streams, check_range=False)
+            if feats is not None:
+                f = feats.batch([sample_views(i) for i in range(i0, i0 + len(items))], out=fbufs)
+                out = model(imgs, proj, depth_values, ins, streams=streams, check_range=False, features=f)
+            else:
+                out = model(imgs, proj, depth_values, ins, streams=streams, check_range=False)
             maps.add(refs[i0:i0 + len(items)], out, imgs=imgs, cams=proj_host["stage3"][:, 0])
     model.DepthNet.check_range()
     return maps.fuse(os.path.join(datapath, scan, "pair.txt"), plyfilename, **fuse_kwargs)

@@ -397,6 +397,25 @@ int damvs_scene_ingest(void* stream, int B, int H, int W, int V, const float* de
 int damvs_scene_inputs(void* stream, int n_images, int H0, int W0, int H, int W, int V,
                        const unsigned char* rgb_store, const int* slots, float* out);
 
+/* ------------------------------------------------------------------ scene features (f1)
+ * A batch's FeatureNet outputs, gathered from scene stores in which every view's features were written once (FeatureNet's
+ * output depends on the image alone; scene.SceneFeatures). For pair i < n_pairs (a sample's view) and tensor k < K:
+ *   outs[k] + i * view_bytes[k]  <-  stores[k] + slots[i] * view_bytes[k]        view_bytes[k] bytes
+ * stores[k] holds V blocks of view_bytes[k] bytes, outs[k] n_pairs of them. The call moves bytes and knows nothing of
+ * dtype or shape, so one launch serves the three stages' tensors, whose sizes differ, in either storage type.
+ * stores, view_bytes, slots and outs are HOST arrays (K, K, n_pairs and K entries); slots may repeat. They are copied
+ * into the kernel arguments, so the call needs no device memory of its own, does not synchronise, and can be captured
+ * into a graph. One launch on `stream`: blockIdx.z the pair, blockIdx.y the tensor, blockIdx.x striding over the view's
+ * 16-byte vectors with min(blocks the largest tensor needs, 2048 / (n_pairs * K)) blocks of 256 threads.
+ * Errors (before any device work), with a message that names the argument:
+ *   DAMVS_E_ARG    a null pointer (an array or one of its K entries), a store or out that is not 16-byte aligned;
+ *   DAMVS_E_SHAPE  n_pairs outside 1..DAMVS_FEATURES_MAX_PAIRS, K outside 1..DAMVS_FEATURES_MAX_TENSORS, V < 1, a slot
+ *                  outside [0, V), a view_bytes[k] that is 0, not a multiple of 16, or >= 2^31. */
+#define DAMVS_FEATURES_MAX_PAIRS 128
+#define DAMVS_FEATURES_MAX_TENSORS 4
+int damvs_feature_gather(void* stream, int n_pairs, int K, int V, const void* const* stores,
+                         const unsigned long long* view_bytes, const int* slots, void* const* outs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,11 @@ pair.txt in which every view lists all the others. Wall clock from the loaded mo
   (b) memory  scene.reconstruct_scene;
   (c) device  scene.reconstruct_scene(inputs="device"): the views decoded to uint8 in threads, uploaded once each,
               converted, resized and batched by damvs_scene_inputs.
-One warm-up of each, then --repeats runs of each, interleaved; the median and the spread of each and the ratios (b) / (a)
-and (c) / (b) of the medians. The PLYs of (a) and (b) are asserted byte-identical (the images are lossless), and (c)'s
+  (d) cached  scene.reconstruct_scene(inputs="device", features="scene"): as (c), and every view through FeatureNet
+              once into a scene.SceneFeatures, each batch's features gathered by damvs_feature_gather.
+One warm-up of each, then --repeats runs of each, interleaved; the median and the spread of each and the ratios (b) / (a),
+(c) / (b) and (d) / (c) of the medians. The PLYs of (c) and (d) are asserted byte-identical at any size (they share
+their images). The PLYs of (a) and (b) are asserted byte-identical (the images are lossless), and (c)'s
 too when the scene needs no resize (--H0 x --W0, the size of the image files, equal to the working size, the default);
 otherwise the `imgs` of (c)'s and (b)'s first batch are asserted to agree within 2^-21 (tests/test_inputs.py). With synthetic weights the depth
 maps are noise and the cloud is small or empty: the tool measures the plumbing around the forward, which is the same
@@ -25,6 +28,10 @@ Then the inputs launch alone (damvs_scene_inputs, B * N = 20 images of 1200 x 16
 scale_mvs_input gives DTU, from a store of --views slots), timed the same way, and a one-off breakdown of (b)'s wall
 clock (`breakdown`): the same steps as reconstruct_scene's host path, one run, with a device synchronisation after
 every device step so that each step's time is its own; the sum is therefore a little above an unsynchronised run.
+The same for (c) and (d) (`device_breakdown`: decode and upload, the FeatureNet fill pass, the inputs launches, the
+gathers, the forwards, the ingests, the fusion), with the cache's size, and the gather launch alone
+(damvs_feature_gather, B * N = 20 pairs of the working size's three stage tensors in bf16 from a store of --views
+slots), timed as the other launches, with the bytes it moves.
 One JSON line, appended to --out when given.
 """
 import argparse
@@ -95,10 +102,102 @@ def file_path(net, data, scan, out_dir, ply, a):
     return fusion.fuse_scene(os.path.join(data, scan), scan_out, scan_out, ply, save_masks=False)
 
 
-def memory_path(net, data, scan, ply, a, inputs="host"):
+def memory_path(net, data, scan, ply, a, inputs="host", features="batch"):
     from damvsnet_amd import scene
+    kw = {"features": features} if features != "batch" else {}
     return scene.reconstruct_scene(net, data, scan, ply, nviews=a.nviews, max_h=a.H, max_w=a.W, batch=a.batch,
-                                   inputs=inputs)
+                                   inputs=inputs, **kw)
+
+
+def device_breakdown(net, data, scan, ply, a, features):
+    """(c)'s (features="batch") or (d)'s ("scene") steps, one run, each timed on its own: what
+    reconstruct_scene(inputs="device") does, with a device synchronisation after every device step."""
+    from damvsnet_amd import mvsio, scene
+    t = {k: 0.0 for k in ("cameras", "decode_upload", "fill", "inputs", "gather", "forward", "ingest", "fuse")}
+
+    def timed(name, fn):
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        t[name] += time.perf_counter() - t0
+        return r
+
+    torch.cuda.synchronize()
+    start = time.perf_counter()
+    ds = mvsio.EvalScenes(data, [scan], a.nviews, max_h=a.H, max_w=a.W, cache_views=True)
+    refs = [ref for _, ref, _ in ds.metas]
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    samples = timed("cameras", lambda: [ds.cameras(i) for i in range(len(ds))])
+    (H0, W0), (H, W) = samples[0]["original_size"], samples[0]["size"]
+    store = scene.SceneInputs(sorted({v for s in samples for v in s["view_ids"]}), H0, W0, H, W, "cuda")
+    timed("decode_upload", lambda: [store.put(v, mvsio.read_img_bytes(ds._img_path(scan, v))) for v in store.view_ids])
+    feats, maps, reused, nbytes = None, None, None, 0
+    with torch.no_grad():
+        if features == "scene":
+            feats = scene.SceneFeatures(net, store.view_ids, H, W, "cuda")
+            nbytes = feats.nbytes
+            for i0 in range(0, len(store.view_ids), a.batch * a.nviews):
+                group = store.view_ids[i0:i0 + a.batch * a.nviews]
+                imgs = timed("inputs", lambda: store.batch([[v] for v in group], out=reused))
+                reused = imgs if reused is None else reused
+                timed("fill", lambda: feats.put(group, imgs[:, 0]))
+            fbufs = feats.buffers(min(a.batch, len(samples)) * a.nviews)
+        for i0 in range(0, len(samples), a.batch):
+            items = samples[i0:i0 + a.batch]
+            lists = [it["view_ids"][:1] if feats is not None else it["view_ids"] for it in items]
+            imgs = timed("inputs", lambda: store.batch(lists, out=reused))
+            reused = imgs if reused is None else reused
+            proj_host = {k: np.stack([it["proj_matrices"][k] for it in items]) for k in items[0]["proj_matrices"]}
+            proj = {k: up(v) for k, v in proj_host.items()}
+            ins = {k: up(np.stack([it["intrinsics_matrices"][k] for it in items]))
+                   for k in items[0]["intrinsics_matrices"]}
+            dv = up(np.stack([it["depth_values"] for it in items]))
+            if feats is not None:
+                f = timed("gather", lambda: feats.batch([it["view_ids"] for it in items], out=fbufs))
+                out = timed("forward", lambda: net(imgs, proj, dv, ins, check_range=False, features=f))
+            else:
+                out = timed("forward", lambda: net(imgs, proj, dv, ins, check_range=False))
+            if maps is None:
+                maps = scene.SceneMaps(refs, H, W, "cuda")
+            timed("ingest", lambda: maps.add(refs[i0:i0 + len(items)], out, imgs=imgs, cams=proj_host["stage3"][:, 0]))
+    net.DepthNet.check_range()
+    n = timed("fuse", lambda: maps.fuse(os.path.join(data, scan, "pair.txt"), ply))
+    total = time.perf_counter() - start
+    res = {k: round(v, 4) for k, v in t.items()}
+    res.update(total_s=round(total, 4), other_s=round(total - sum(t.values()), 4), points=n,
+               forward_share=round(t["forward"] / total, 4), cache_MB=round(nbytes / 1e6, 1))
+    return res
+
+
+def features_bench(a, H, W, calls=20, blocks=5):
+    """damvs_feature_gather alone: B * N = 20 pairs of the three stage tensors of an H x W image in bf16."""
+    from damvsnet_amd import _capi
+    lib = _capi.load_library()
+    n, V, es = 20, a.views, 2
+    view_bytes = [H // 4 * (W // 4) * 32 * es, H // 2 * (W // 2) * 16 * es, H * W * 8 * es]
+    g = torch.Generator(device="cuda").manual_seed(0)
+    stores = [torch.randint(0, 256, (V, vb), device="cuda", dtype=torch.uint8, generator=g) for vb in view_bytes]
+    outs = [torch.empty(n, vb, device="cuda", dtype=torch.uint8) for vb in view_bytes]
+    args = ((ctypes.c_void_p * 3)(*[t.data_ptr() for t in stores]), (ctypes.c_ulonglong * 3)(*view_bytes),
+            (ctypes.c_int * n)(*[(3 * i + 1) % V for i in range(n)]), (ctypes.c_void_p * 3)(*[t.data_ptr() for t in outs]))
+    call = lambda: _capi.check(lib.damvs_feature_gather(_capi.stream_ptr(), n, 3, V, *args))
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(blocks):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / calls)
+    moved = n * sum(view_bytes)
+    med = float(np.median(ms))
+    return {"pairs": n, "shape": [H, W], "dtype": "bf16", "calls_per_block": calls,
+            "ms_per_call_blocks": [round(m, 4) for m in ms], "ms_per_call": round(med, 4), "bytes_read": moved,
+            "bytes_written": moved, "GBps": round(2 * moved / med / 1e6, 1)}
 
 
 def breakdown(net, data, scan, ply, a):
@@ -271,17 +370,19 @@ def main():
         new_w, new_h, _ = mvsio.scale_mvs_camera(H0, W0, np.eye(3, dtype=np.float32), a.W, a.H)
         resized = (new_h, new_w) != (H0, W0)
         print("scene written: %d views at %d x %d, working size %d x %d" % (a.views, H0, W0, new_h, new_w), flush=True)
-        names = ("files", "memory", "device")
+        names = ("files", "memory", "device", "cached")
         times, counts = {k: [] for k in names}, {}
         read = lambda name: open(os.path.join(root, name + ".ply"), "rb").read()
         for rep in range(a.repeats + 1):  # run 0 is the warm-up of each
-            for name in names[rep % 3:] + names[:rep % 3]:
+            for name in names[rep % 4:] + names[:rep % 4]:
                 out_dir, ply = os.path.join(root, "out_" + name), os.path.join(root, name + ".ply")
                 shutil.rmtree(out_dir, ignore_errors=True)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 if name == "files":
                     n = file_path(net, data, scan, out_dir, ply, a)
+                elif name == "cached":
+                    n = memory_path(net, data, scan, ply, a, "device", "scene")
                 else:
                     n = memory_path(net, data, scan, ply, a, "host" if name == "memory" else "device")
                 dt = time.perf_counter() - t0
@@ -293,18 +394,24 @@ def main():
                 "the file path and the memory path wrote different clouds"
             assert resized or (read("device") == read("memory") and counts["device"] == counts["memory"]), \
                 "the device inputs and the host inputs wrote different clouds"
+            assert read("cached") == read("device") and counts["cached"] == counts["device"], \
+                "the cached features and the per-batch features wrote different clouds"
         imgs_diff = first_batch_imgs_diff(data, scan, a) if resized else 0.0
         assert imgs_diff <= 2.0 ** -21, "imgs of the device inputs differ from the host's by %.3e" % imgs_diff
         med = {k: float(np.median(v)) for k, v in times.items()}
         res = {"metric": "seconds, loaded model to PLY on disk", "views": a.views, "image_files": [H0, W0],
                "shape": [new_h, new_w], "nviews": a.nviews, "batch": a.batch, "dtype": "bf16", "ndepths": [48, 32, 8],
-               "points": counts, "ply_identical": {"files_memory": True, "device_memory": not resized},
+               "points": counts, "ply_identical": {"files_memory": True, "device_memory": not resized, "cached_device": True},
                "imgs_max_diff_device_host": imgs_diff}
         for k in names:
             res[k + "_s"], res[k + "_median_s"] = times[k], round(med[k], 3)
             res[k + "_spread_s"] = [min(times[k]), max(times[k])]
         res["ratio_memory_over_files"] = round(med["memory"] / med["files"], 4)
         res["ratio_device_over_memory"] = round(med["device"] / med["memory"], 4)
+        res["ratio_cached_over_device"] = round(med["cached"] / med["device"], 4)
+        res["device_breakdown_s"] = device_breakdown(net, data, scan, os.path.join(root, "breakdown_c.ply"), a, "batch")
+        res["cached_breakdown_s"] = device_breakdown(net, data, scan, os.path.join(root, "breakdown_d.ply"), a, "scene")
+        res["features"] = features_bench(a, new_h, new_w)
         res["memory_breakdown_s"] = breakdown(net, data, scan, os.path.join(root, "breakdown.ply"), a)
         res["ingest"] = ingest_bench(argparse.Namespace(**dict(vars(a), H=new_h, W=new_w)))
         res["inputs"] = inputs_bench(a)
