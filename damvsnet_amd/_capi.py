@@ -122,6 +122,12 @@ SIGNATURES = (
     ("damvs_fusion_cloud_scratch", c_int, (c_int, c_int)),
     ("damvs_fusion_cloud", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
                                    c_void_p, ctypes.c_longlong, c_void_p)),
+    ("damvs_cloud_thin_table_bytes", c_int, (ctypes.c_longlong, ctypes.POINTER(c_size_t))),
+    ("damvs_cloud_thin_hash", c_int, (ctypes.c_ulonglong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong))),
+    ("damvs_cloud_thin_clear", c_int, (c_void_p, c_void_p, ctypes.c_longlong)),
+    ("damvs_cloud_thin", c_int, (c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_float, ctypes.c_longlong, c_void_p,
+                                 ctypes.c_longlong, c_void_p)),
+    ("damvs_cloud_thin_status", c_int, (c_void_p, c_void_p, ctypes.c_longlong)),
     ("damvs_scene_ingest", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, ctypes.c_longlong, ctypes.POINTER(c_int), c_void_p, c_void_p, c_void_p)),
     ("damvs_scene_inputs", c_int, (c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, ctypes.POINTER(c_int),

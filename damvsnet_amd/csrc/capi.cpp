@@ -292,7 +292,7 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #define DAMVS_BUILD_ID "unstamped"
 #endif
 // The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so,
-// libdamvs_inputs.so, libdamvs_features.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
+// libdamvs_inputs.so, libdamvs_features.so, libdamvs_thin.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
   static const std::string id = [] {
     std::string s(DAMVS_BUILD_ID);
@@ -300,7 +300,8 @@ const char* damvs_build_id(void) {
                                                         {"libdamvs_cloud.so", fusion_cloud_build_id()},
                                                         {"libdamvs_scene.so", scene_build_id()},
                                                         {"libdamvs_inputs.so", inputs_build_id()},
-                                                        {"libdamvs_features.so", features_build_id()}};
+                                                        {"libdamvs_features.so", features_build_id()},
+                                                        {"libdamvs_thin.so", thin_build_id()}};
     for (const auto& l : side)
       if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
     return s;
@@ -1087,6 +1088,88 @@ int damvs_feature_gather(void* stream, int n_pairs, int K, int V, const void* co
   }
   for (int i = n_pairs; i < kFeaturesMaxPairs; ++i) a.slots[i] = 0;
   return hip_check(launch_feature_gather(static_cast<hipStream_t>(stream), n_pairs, K, a), "feature_gather launch");
+}
+
+// ============================================================================ voxel thinning
+namespace {
+
+// keys[slots], owners[slots], then the status word (8 bytes keep the size a multiple of 8)
+int thin_slots_ok(long long slots) {
+  if (slots < kThinMinSlots || slots > kThinMaxSlots || (slots & (slots - 1)) != 0)
+    return fail(DAMVS_E_ARG, "slots %lld is not a power of two in [%lld, 2^32]", slots, kThinMinSlots);
+  return DAMVS_OK;
+}
+
+unsigned* thin_status_word(void* table, long long slots) {
+  return reinterpret_cast<unsigned*>(static_cast<unsigned char*>(table) + (size_t)slots * 16);
+}
+
+}  // namespace
+
+int damvs_cloud_thin_table_bytes(long long slots, size_t* bytes) {
+  if (!bytes) return fail(DAMVS_E_ARG, "null bytes");
+  DAMVS_TRY(thin_slots_ok(slots));
+  *bytes = (size_t)slots * 16 + 8;
+  return DAMVS_OK;
+}
+
+int damvs_cloud_thin_hash(unsigned long long key, long long slots, long long* slot) {
+  if (!slot) return fail(DAMVS_E_ARG, "null slot");
+  DAMVS_TRY(thin_slots_ok(slots));
+  *slot = (long long)thin_hash(key, (unsigned long long)slots);
+  return DAMVS_OK;
+}
+
+int damvs_cloud_thin_clear(void* stream, void* table, long long slots) {
+  if (!table) return fail(DAMVS_E_ARG, "null table");
+  DAMVS_TRY(thin_slots_ok(slots));
+  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(DAMVS_E_ARG, "table is not 8-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DAMVS_TRY(hip_check(hipMemsetAsync(table, 0xFF, (size_t)slots * 16, s), "table clear"));
+  return hip_check(hipMemsetAsync(thin_status_word(table, slots), 0, 8, s), "status clear");
+}
+
+int damvs_cloud_thin(void* stream, long long n, const unsigned char* mask, const float* xyz, float inv_voxel,
+                     long long base, void* table, long long slots, unsigned char* keep) {
+  if (!mask) return fail(DAMVS_E_ARG, "null mask");
+  if (!xyz) return fail(DAMVS_E_ARG, "null xyz");
+  if (!table) return fail(DAMVS_E_ARG, "null table");
+  if (!keep) return fail(DAMVS_E_ARG, "null keep");
+  if (n < 1 || n >= (1LL << 31)) return fail(DAMVS_E_SHAPE, "n %lld not in [1, 2^31)", n);
+  DAMVS_TRY(thin_slots_ok(slots));
+  if (!(inv_voxel > 0.f) || !(inv_voxel <= 3.402823466e38f))
+    return fail(DAMVS_E_ARG, "inv_voxel %g is not finite and positive", (double)inv_voxel);
+  if (base < 0 || base > (1LL << 62)) return fail(DAMVS_E_ARG, "base %lld not in [0, 2^62]", base);
+  if (reinterpret_cast<uintptr_t>(table) & 7) return fail(DAMVS_E_ARG, "table is not 8-byte aligned");
+  ThinArgs a;
+  a.n = n;
+  a.mask = mask;
+  a.xyz = xyz;
+  a.inv_voxel = inv_voxel;
+  a.base = (unsigned long long)base;
+  a.keys = static_cast<unsigned long long*>(table);
+  a.owners = a.keys + slots;
+  a.status = thin_status_word(table, slots);
+  a.slots = (unsigned long long)slots;
+  a.keep = keep;
+  return hip_check(launch_cloud_thin(static_cast<hipStream_t>(stream), a), "cloud_thin launch");
+}
+
+int damvs_cloud_thin_status(void* stream, void* table, long long slots) {
+  if (!table) return fail(DAMVS_E_ARG, "null table");
+  DAMVS_TRY(thin_slots_ok(slots));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned* word = thin_status_word(table, slots);
+  unsigned v = 0;
+  DAMVS_TRY(hip_check(hipMemcpyAsync(&v, word, 4, hipMemcpyDeviceToHost, s), "status copy"));
+  DAMVS_TRY(hip_check(hipMemsetAsync(word, 0, 4, s), "status clear"));
+  DAMVS_TRY(hip_check(hipStreamSynchronize(s), "hipStreamSynchronize"));
+  if (v & kThinRange)
+    return fail(DAMVS_E_RANGE, "voxel thinning: a selected point is not finite or its cell index lies outside "
+                               "[-2^20, 2^20) (out of range%s)", (v & kThinFull) ? "; the table was full as well" : "");
+  if (v & kThinFull)
+    return fail(DAMVS_E_WORKSPACE, "voxel thinning: the table of %lld slots is full (table full)", slots);
+  return DAMVS_OK;
 }
 
 }  // extern "C"

@@ -254,6 +254,39 @@ unsigned feature_gather_grid_x(int n_pairs, int K, unsigned max_nvec);
 hipError_t launch_feature_gather(hipStream_t s, int n_pairs, int K, const FeaturesArgs& a);
 const char* features_build_id();
 
+// ---------------------------------------------------------------- voxel thinning (k_thin.hip, libdamvs_thin.so)
+constexpr int kThinBlock = 256;                    // threads, one pixel each
+constexpr unsigned long long kThinEmpty = ~0ull;   // an unclaimed slot's key and owner; no cell key (63 bits) equals it
+constexpr unsigned kThinFull = 1u, kThinRange = 2u;  // bits of the status word
+constexpr long long kThinMinSlots = 64, kThinMaxSlots = 1LL << 32;
+// The slot a key's probe starts from (slots a power of two): MurmurHash3's 64-bit finalizer, so that the keys of
+// neighbouring cells, which differ in a few low bits of three 21-bit fields, start from unrelated slots.
+// The kept points never depend on it (they are the first of their cell in cloud order); damvs_cloud_thin_hash hands it
+// to the tests that place probe chains.
+__host__ __device__ inline unsigned long long thin_hash(unsigned long long key, unsigned long long slots) {
+  key ^= key >> 33;
+  key *= 0xff51afd7ed558ccdull;
+  key ^= key >> 33;
+  key *= 0xc4ceb9fe1a85ec53ull;
+  key ^= key >> 33;
+  return key & (slots - 1ull);
+}
+struct ThinArgs {
+  long long n;                // H * W, in [1, 2^31)
+  const unsigned char* mask;  // [n] as the fusion kernels write it; bit value 4 (final) selects
+  const float* xyz;           // [n][3]
+  float inv_voxel;            // float32(1) / float32(voxel), formed by the caller
+  unsigned long long base;    // ordinal of the view's pixel 0: the sum of n over the views claimed before
+  unsigned long long* keys;   // [slots]
+  unsigned long long* owners; // [slots] the lowest ordinal that claimed the slot's key
+  unsigned* status;           // kThinFull | kThinRange, set by atomic OR
+  unsigned long long slots;   // a power of two in [kThinMinSlots, kThinMaxSlots]
+  unsigned char* keep;        // [n] 4 where the pixel owns its cell, else 0
+};
+// claim, then resolve, on s
+hipError_t launch_cloud_thin(hipStream_t s, const ThinArgs& a);
+const char* thin_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -18,6 +18,11 @@ dist_base 1/4, rel_diff_base 1/1300, thres_view 5.
 `fuse_scene` is filter_depth with the scene kept on the device: every map uploaded once, and the coloured points of
 each view appended in pixel order to one device buffer by `compact_cloud` (k_cloud.hip, damvs_fusion_cloud), so that
 one copy of count * 15 bytes is the PLY's body. Same files in, same files out.
+
+`voxel=` on the scene-level drivers (fuse_scene, fuse_resident, scene.SceneMaps.fuse, scene.reconstruct_scene) thins
+the cloud on the device, between the fusion kernel and compact_cloud: at most one point per cell of an axis-aligned
+grid of that edge, the first one in PLY order (VoxelGrid, k_thin.hip; `voxel_first` is the rule in numpy). The records
+are unchanged, so the thinned PLY is a subsequence of the unthinned one. voxel=None, the default, is the path above.
 """
 from __future__ import annotations
 
@@ -133,6 +138,139 @@ def compact_cloud(mask, xyz, rgb, records, cursor, scratch=None):
     return scratch
 
 
+# ------------------------------------------------------------------------------------------------ voxel thinning
+VOXEL_Q = 1 << 20  # cell indices lie in [-2^20, 2^20) per axis
+_EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+
+
+def _inv_voxel(voxel):
+    """float32(1) / float32(voxel) as a Python float; ValueError unless voxel and the quotient are finite and > 0."""
+    try:
+        with np.errstate(all="ignore"):
+            v = np.float32(voxel)
+            inv = np.float32(1) / v
+    except (TypeError, ValueError):
+        raise ValueError("voxel must be a positive finite number (got %r)" % (voxel,)) from None
+    if not (np.isfinite(v) and v > 0 and np.isfinite(inv) and inv > 0):
+        raise ValueError("voxel must be a positive finite number whose float32 reciprocal is one too (got %r)" % (voxel,))
+    return float(inv)
+
+
+def _voxel_slots(voxel_slots, pixels=None):
+    """The table's slot count: voxel_slots checked (a power of two in [64, 2^32]), or, for None, the power of two at or
+    above twice `pixels`."""
+    if voxel_slots is None:
+        return max(64, 1 << (2 * int(pixels) - 1).bit_length())
+    ok = isinstance(voxel_slots, (int, np.integer)) and not isinstance(voxel_slots, bool) and \
+        64 <= voxel_slots <= 1 << 32 and voxel_slots & (voxel_slots - 1) == 0
+    if not ok:
+        raise ValueError("voxel_slots must be a power of two in [64, 2^32] (got %r)" % (voxel_slots,))
+    return int(voxel_slots)
+
+
+def check_voxel(voxel, voxel_slots):
+    """The drivers' argument check, before anything is launched or written: ValueError for a voxel that is not a
+    positive finite number, a voxel_slots that is not a power of two in [64, 2^32], or voxel_slots without voxel."""
+    if voxel is None:
+        if voxel_slots is not None:
+            raise ValueError("voxel_slots=%r without voxel" % (voxel_slots,))
+        return
+    _inv_voxel(voxel)
+    if voxel_slots is not None:
+        _voxel_slots(voxel_slots)
+
+
+def voxel_keys(xyz, voxel):
+    """The thinning rule's cell keys on the CPU: xyz (n, 3) -> (keys uint64 (n,), in_range bool (n,)).
+    inv = float32(1) / float32(voxel); q = floor(float32(x) * inv) per axis (one float32 multiply, floor, integer); a
+    point is in range when every q lies in [-2^20, 2^20) (NaN and infinities do not); key = (qx + 2^20) |
+    (qy + 2^20) << 21 | (qz + 2^20) << 42, all ones where out of range."""
+    inv = np.float32(_inv_voxel(voxel))
+    p = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        q = np.floor(p * inv)
+        ok = ((q >= -VOXEL_Q) & (q < VOXEL_Q)).all(axis=1)
+    u = (np.where(ok[:, None], q, 0).astype(np.int64) + VOXEL_Q).astype(np.uint64)
+    keys = u[:, 0] | (u[:, 1] << np.uint64(21)) | (u[:, 2] << np.uint64(42))
+    return np.where(ok, keys, _EMPTY), ok
+
+
+def voxel_first(xyz, voxel):
+    """The thinning rule in numpy: the indices, ascending, of the points of xyz (n, 3) that are the first, in order,
+    of their cell of the grid of edge `voxel` (voxel_keys). ValueError when a point is not finite or out of range."""
+    keys, ok = voxel_keys(xyz, voxel)
+    if not ok.all():
+        bad = int(np.flatnonzero(~ok)[0])
+        raise ValueError("point %d %s is not finite or its cell index lies outside [-2^20, 2^20) at voxel %r (out of "
+                         "range)" % (bad, np.asarray(xyz, dtype=np.float32).reshape(-1, 3)[bad].tolist(), voxel))
+    _, first = np.unique(keys, return_index=True)
+    return np.sort(first).astype(np.int64)
+
+
+def voxel_home_slot(key, slots):
+    """The slot a cell key's probe starts from in a table of `slots` slots (damvs_cloud_thin_hash, the device's
+    function run on the host): for tests that place probe chains; the kept points never depend on it."""
+    out = ctypes.c_longlong()
+    check(_capi.load_library().damvs_cloud_thin_hash(int(key), int(slots), ctypes.byref(out)))
+    return int(out.value)
+
+
+class VoxelGrid:
+    """One scene's voxel table on the device (damvs_cloud_thin, k_thin.hip): `slots` 64-bit keys and owners and a
+    status word, `nbytes` = 16 * slots + 8 bytes. voxel: the cell's edge in world units; slots: a power of two in
+    [64, 2^32], at least the number of occupied cells (twice that keeps the probe chains short).
+    claim(mask, xyz, base) per reference view in PLY order, on one stream; check() once at the end."""
+
+    def __init__(self, voxel, slots, device="cuda"):
+        self.inv_voxel = _inv_voxel(voxel)
+        self.slots = _voxel_slots(slots) if slots is not None else _voxel_slots(None, 32)
+        self.voxel = float(voxel)
+        self._lib = _capi.load_library()
+        nbytes = ctypes.c_size_t()
+        check(self._lib.damvs_cloud_thin_table_bytes(self.slots, ctypes.byref(nbytes)))
+        self.nbytes = int(nbytes.value)
+        self.table = torch.empty(self.nbytes // 8, device=device, dtype=torch.int64)
+        self.clear()
+
+    def clear(self):
+        """Empty the table and the status (two memsets on the current stream)."""
+        check(self._lib.damvs_cloud_thin_clear(_capi.stream_ptr(self.table.device), self.table.data_ptr(), self.slots))
+
+    def claim(self, mask, xyz, base, keep=None):
+        """One view: mask (H, W) or (n,) uint8 (bit value 4 selects), xyz (..., 3) float32 of the same pixels, base:
+        the number of pixels of the views claimed before (pixel p's ordinal is base + p). -> keep, uint8 of mask's
+        shape (given, or allocated): 4 where the pixel is the first of its cell so far, else 0: the mask compact_cloud
+        takes. Two launches on the current stream, nothing synchronised; a later view never takes a cell from an
+        earlier one."""
+        dev = self.table.device
+        ok = lambda t, dt: t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
+        if not (ok(mask, torch.uint8) and ok(xyz, torch.float32) and tuple(xyz.shape) == tuple(mask.shape) + (3,)
+                and mask.numel() >= 1):
+            raise ValueError("claim takes contiguous CUDA tensors of the table's device: mask (...) uint8, xyz (..., 3) "
+                             "float32")
+        if keep is None:
+            keep = torch.empty_like(mask)
+        elif not (ok(keep, torch.uint8) and keep.shape == mask.shape):
+            raise ValueError("keep must be a contiguous uint8 CUDA tensor of mask's shape")
+        check(self._lib.damvs_cloud_thin(_capi.stream_ptr(dev), mask.numel(), mask.data_ptr(), xyz.data_ptr(),
+                                         self.inv_voxel, int(base), self.table.data_ptr(), self.slots, keep.data_ptr()))
+        return keep
+
+    def check(self):
+        """Synchronises the current stream. ValueError with the library's message when, since the last check or clear,
+        a selected point was out of range or the table was full; the status is clear afterwards."""
+        rc = self._lib.damvs_cloud_thin_status(_capi.stream_ptr(self.table.device), self.table.data_ptr(), self.slots)
+        if rc != 0:
+            msg = self._lib.damvs_last_error_string().decode(errors="replace")
+            if rc == -6:
+                msg += ": raise voxel_slots"
+            raise ValueError("%s (%d): %s" % (_capi.ERRORS.get(rc, "DAMVS_E_?"), rc, msg))
+
+    def occupied(self):
+        """Slots that hold a key (synchronises): the table's load factor is occupied() / slots."""
+        return int((self.table[:self.slots] != -1).sum().item())
+
+
 def _save_mask(path, m):
     from PIL import Image
     Image.fromarray(m.astype(np.uint8) * 255).save(path)
@@ -172,17 +310,20 @@ def filter_depth(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0
 
 
 def fuse_scene(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25,
-               rel_diff_base=1 / 1300, device="cuda", method="dypcd", thres_view=5, save_masks=True, max_points=None):
+               rel_diff_base=1 / 1300, device="cuda", method="dypcd", thres_view=5, save_masks=True, max_points=None,
+               voxel=None, voxel_slots=None):
     """filter_depth's files in, filter_depth's files out, with the scene kept on the device: every view's depth map,
     camera and (for reference views) three confidences and image are read and uploaded once; each reference view
     runs the fusion kernel and compact_cloud appends its coloured points to one record buffer behind one device
     cursor, with no host synchronisation between views; the masks come back only for the PNGs (save_masks) and the
     cloud in one copy of count * 15 bytes, written by mvsio.write_ply_records.
     The buffer holds the sum of H * W over the reference views (an exact upper bound) or max_points if that is less;
-    a scene that needs more raises ValueError with the count needed and writes no PLY. Returns the point count."""
+    a scene that needs more raises ValueError with the count needed and writes no PLY. Returns the point count.
+    voxel, voxel_slots: thin the cloud to one point per cell (fuse_resident's docstring)."""
     from PIL import Image
     if method not in METHODS:
         raise ValueError("fusion method %r not in %s" % (method, METHODS))
+    check_voxel(voxel, voxel_slots)
     pairs = mvsio.read_pair_file(os.path.join(pair_folder, "pair.txt"))
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     pfm = lambda kind, v, sfx="": up(mvsio.read_pfm(os.path.join(out_folder, kind, "%08d%s.pfm" % (v, sfx)))[0])
@@ -201,20 +342,36 @@ def fuse_scene(pair_folder, scan_folder, out_folder, plyfilename, conf=(0.1, 0.1
                     ref_view, img.dtype, img.shape, tuple(depths[ref_view].shape) + (3,)))
             rgbs[ref_view] = up(img)
     return fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf, dist_base, rel_diff_base, method,
-                         thres_view, os.path.join(out_folder, "mask") if save_masks else None, max_points, device)
+                         thres_view, os.path.join(out_folder, "mask") if save_masks else None, max_points, device,
+                         voxel, voxel_slots)
 
 
 def fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25,
-                  rel_diff_base=1 / 1300, method="dypcd", thres_view=5, mask_dir=None, max_points=None, device="cuda"):
+                  rel_diff_base=1 / 1300, method="dypcd", thres_view=5, mask_dir=None, max_points=None, device="cuda",
+                  voxel=None, voxel_slots=None):
     """The per-pair loop of fuse_scene and scene.SceneMaps.fuse over maps already on the device: dicts by view id of
     cams (K, E) host arrays, depths (H, W) float32, and for the reference views confs (final, stage 2, stage 1) and rgbs
     (H, W, 3) uint8. Per pair the fusion kernel and compact_cloud on one cursor, no host synchronisation between views;
     then the mask PNGs (mask_dir, None: not written), one copy of count * 15 bytes and mvsio.write_ply_records.
-    Raises ValueError, writing no PLY, when the cloud does not fit max_points. Returns the point count."""
+    Raises ValueError, writing no PLY, when the cloud does not fit max_points. Returns the point count.
+    voxel: None, or the edge in world units of an axis-aligned grid: the PLY then holds at most one point per cell, the
+    first one in PLY order (reference views in pair order, pixels row-major) with its record unchanged, so it is a
+    subsequence of the voxel=None PLY (voxel_first over that PLY's points gives the indices). Between the fusion kernel
+    and compact_cloud a VoxelGrid.claim (two launches) turns the view's mask into the mask of the pixels that are the
+    first of their cell; still no host synchronisation between views. The mask PNGs remain the fusion's masks and
+    max_points bounds the thinned count. voxel_slots: the table's slots, a power of two in [64, 2^32]; None: the power of
+    two at or above twice the sum of H * W over the reference views, which cannot fill. The table takes 16 bytes per
+    slot: 2^28 slots, 4.3 GB, for 49 views at 1184 x 1600 (93 M pixels) on a 288 GB device; a scene whose occupied cells
+    are known to be fewer can pass less. A table that fills, or a kept point that is not finite or whose cell index
+    leaves [-2^20, 2^20), raises ValueError and writes no PLY. A bad voxel (not a positive finite number) or voxel_slots
+    raises ValueError before anything is launched."""
     if method not in METHODS:
         raise ValueError("fusion method %r not in %s" % (method, METHODS))
+    check_voxel(voxel, voxel_slots)
     save_masks = mask_dir is not None
     capacity = sum(depths[r].numel() for r, _ in pairs)
+    grid = None if voxel is None else VoxelGrid(voxel, _voxel_slots(voxel_slots, max(capacity, 1)), device)
+    base, keeps = 0, {}
     if max_points is not None:
         capacity = max(0, min(capacity, int(max_points)))
     records = torch.empty(capacity * RECORD_BYTES, device=device, dtype=torch.uint8)
@@ -226,7 +383,11 @@ def fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf=(0.1, 0.15
         _, mask, xyz = _fuse_view_raw(depths[ref_view], K_ref, E_ref, srcs, confs[ref_view], conf, dist_base,
                                       rel_diff_base, True, method, thres_view, 1.0, 0.01)
         shape = tuple(mask.shape)
-        scratch[shape] = compact_cloud(mask, xyz, rgbs[ref_view], records, cursor, scratch.get(shape))
+        chosen = mask
+        if grid is not None:
+            chosen = keeps[shape] = grid.claim(mask, xyz, base, keeps.get(shape))
+            base += mask.numel()
+        scratch[shape] = compact_cloud(chosen, xyz, rgbs[ref_view], records, cursor, scratch.get(shape))
         if save_masks:
             masks.append((ref_view, mask))
     if save_masks:
@@ -235,6 +396,8 @@ def fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf=(0.1, 0.15
             m = mask.cpu().numpy()
             for bit, kind in ((1, "photo"), (2, "geo"), (4, "final")):
                 _save_mask(os.path.join(mask_dir, "%08d_%s.png" % (ref_view, kind)), (m & bit) != 0)
+    if grid is not None:
+        grid.check()
     count = int(cursor.item())
     if count > capacity:
         raise ValueError("the scene's point cloud needs %d points, the record buffer holds %d" % (count, capacity))

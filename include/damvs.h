@@ -37,8 +37,9 @@ enum {
   DAMVS_E_DTYPE = -3,     /* unsupported storage type */
   DAMVS_E_HIP = -4,       /* HIP runtime error */
   DAMVS_E_NOMEM = -5,     /* device allocation failed (create only) */
-  DAMVS_E_WORKSPACE = -6, /* workspace too small */
-  DAMVS_E_RANGE = -7      /* non-finite depth / confidence / variance (damvs_stage_status) */
+  DAMVS_E_WORKSPACE = -6, /* workspace too small; a full voxel table (damvs_cloud_thin_status) */
+  DAMVS_E_RANGE = -7      /* non-finite depth / confidence / variance (damvs_stage_status); a point outside the voxel
+                             grid (damvs_cloud_thin_status) */
 };
 
 enum { DAMVS_F32 = 0, DAMVS_BF16 = 1 };                       /* storage of features / volumes */
@@ -345,6 +346,45 @@ int damvs_fusion_cloud_scratch(int H, int W);
 int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, const float* xyz, const unsigned char* rgb,
                        unsigned int* scratch, long long scratch_elems, unsigned char* records, long long capacity,
                        unsigned long long* cursor);
+
+/* ------------------------------------------------------------------ voxel-thinned cloud (f4)
+ * At most one point per cell of an axis-aligned grid, chosen on the device between the fusion kernel and
+ * damvs_fusion_cloud: of a scene's selected pixels (mask bit value 4), the first one in cloud order of every cell is
+ * kept. Cloud order is the PLY's: the views in the order of the calls, row-major pixels inside a view; pixel p of a call
+ * has the ordinal base + p, base = the sum of n over the calls before it on this table (a host number).
+ * The rule, per selected pixel with point (x, y, z) of xyz [n][3]:
+ *   q = floor(x * inv_voxel) per axis (one float32 multiply, floor, integer), inv_voxel = float32(1) / float32(edge)
+ *   formed by the caller; the pixel is in range when -2^20 <= q < 2^20 on all three axes (NaN and infinities are not);
+ *   cell key = (qx + 2^20) | (qy + 2^20) << 21 | (qz + 2^20) << 42, 63 bits; all ones marks an empty slot.
+ *   keep[p] = 4 if and only if no selected in-range pixel of a lower ordinal has the same key; else 0 (unselected and
+ *   out-of-range pixels too). keep [n] is a mask in the form damvs_fusion_cloud takes.
+ * The table is one open-addressing hash table per scene: `slots` 64-bit keys, `slots` 64-bit owners (the lowest ordinal
+ * that claimed the key), then a status word: *bytes of damvs_cloud_thin_table_bytes (16 * slots + 8; the size passes
+ * 2^31 from 2^27 slots on, hence the out-parameter, as damvs_stage_workspace_size has) of device memory, 8-byte aligned,
+ * slots a power of two in [64, 2^32]. damvs_cloud_thin_clear empties it (one hipMemsetAsync of the slots to all ones,
+ * one of the status) and must run, on the same stream, before the scene's first damvs_cloud_thin.
+ * damvs_cloud_thin is two launches on `stream`: claim (per selected pixel, linear probing from a hash of the key; per
+ * slot a 64-bit compare-and-swap empty -> key and, when it returned empty or the key, a 64-bit unsigned atomic min of
+ * the ordinal into the owner; every decision rests on an atomic's returned value; a counted loop of at most `slots`
+ * trips, no thread waits for another) and resolve (plain loads: keep[p] = 4 where the owner is p's ordinal). The kept
+ * set depends on neither the hash, the table size nor the order in which threads arrive, and is bit for bit
+ * reproducible. The call allocates nothing and does not synchronise, so it can be captured into a graph; calls that
+ * share a table must be enqueued on one stream (or otherwise ordered).
+ * A selected pixel out of range, or one that found no slot in a full table, sets a bit of the status word and claims
+ * nothing; keep is then not the rule's. damvs_cloud_thin_status synchronises `stream`, returns DAMVS_OK,
+ * DAMVS_E_RANGE (a selected point out of range) or DAMVS_E_WORKSPACE (the table was full: use more slots), with a
+ * message that names which, and clears the status.
+ * damvs_cloud_thin_hash: *slot = the slot a key's probe starts from in a table of `slots` slots (a host function; for
+ * tests that place probe chains).
+ * Errors (before any device work): a null pointer, a table that is not 8-byte aligned, slots not a power of two in
+ * [64, 2^32], inv_voxel not finite or not positive, base outside [0, 2^62] -> DAMVS_E_ARG; n < 1 or n >= 2^31 ->
+ * DAMVS_E_SHAPE. */
+int damvs_cloud_thin_table_bytes(long long slots, size_t* bytes);
+int damvs_cloud_thin_hash(unsigned long long key, long long slots, long long* slot);
+int damvs_cloud_thin_clear(void* stream, void* table, long long slots);
+int damvs_cloud_thin(void* stream, long long n, const unsigned char* mask, const float* xyz, float inv_voxel,
+                     long long base, void* table, long long slots, unsigned char* keep);
+int damvs_cloud_thin_status(void* stream, void* table, long long slots);
 
 /* ------------------------------------------------------------------ scene ingest (f4)
  * The outputs of one forward over B reference views, written into scene-resident stores that the fusion entry points

@@ -33,6 +33,17 @@ gathers, the forwards, the ingests, the fusion), with the cache's size, and the 
 (damvs_feature_gather, B * N = 20 pairs of the working size's three stage tensors in bf16 from a store of --views
 slots), timed as the other launches, with the bytes it moves.
 One JSON line, appended to --out when given.
+
+--thin runs the voxel-thinning record instead (fusion's voxel= option, k_thin.hip) and prints its own JSON line:
+  * `reconstruct_scene(inputs="device", features="scene")` with voxel=None against --voxels (two edges in world units),
+    interleaved after one warm-up of each, with the point counts and PLY bytes (synthetic weights: the cloud is what the
+    noise gives);
+  * the launches of one reference view of the same scene's cameras, each timed alone (20 back-to-back calls per block
+    between two HIP events, median of 5 blocks): the fusion kernel over fronto-parallel depth maps with 10 sources, then,
+    on the points it wrote, with the mask forced to every pixel and to a random 30 %, compact_cloud and the claim +
+    resolve pair, for an edge of 2 and of 8 pixel footprints (about 4 and 64 pixels per cell and view): view 0 into an
+    empty table (every cell inserted) and the later views of the scan (most cells already taken), with the table's bytes
+    and the load factor after all views.
 """
 import argparse
 import ctypes
@@ -344,8 +355,122 @@ def ingest_bench(a, calls=20, blocks=5):
             "ms_per_call": round(med, 4), "bytes_per_call": int(nbytes), "GBps": round(nbytes / med / 1e6, 1)}
 
 
+def _event_ms(call, calls=20, blocks=5, before=None):
+    """Median over `blocks` of the mean time of `calls` back-to-back calls between two HIP events; `before` runs
+    (untimed, synchronised) ahead of every block."""
+    ms = []
+    for _ in range(blocks + 1):  # block 0 warms up
+        if before is not None:
+            before()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            call()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / calls)
+    return round(float(np.median(ms[1:])), 4)
+
+
+def thin_launches(a, H, W):
+    """The launches of one reference view, each alone: fusion, compact_cloud, claim + resolve (the module docstring)."""
+    from damvsnet_amd import fusion, synth
+    V = a.views
+    proj, _, dv = synth.cameras(1, V, H, W)
+    cams = [(proj["stage3"][0, v, 1, :3, :3].copy(), proj["stage3"][0, v, 0].copy()) for v in range(V)]
+    depth_mid = float(dv[0, 0] + dv[0, -1]) / 2
+    depths = [torch.full((H, W), depth_mid, device="cuda") for _ in range(V)]
+    confs = tuple(torch.ones(H, W, device="cuda") for _ in range(3))
+    nsrc = min(10, V - 1)
+    fuse = lambda v: fusion._fuse_view_raw(depths[v], cams[v][0], cams[v][1],
+                                           [(depths[s],) + cams[s] for s in range(V) if s != v][:nsrc], confs,
+                                           (0.1, 0.15, 0.9), 0.25, 1 / 1300, True, "dypcd", 5, 1.0, 0.01)
+    res = {"shape": [H, W], "sources": nsrc, "fusion_ms": _event_ms(lambda: fuse(0))}
+    xyzs = []
+    for v in range(V):  # the world points of every pixel of every view, whatever the filter kept
+        u, w = torch.meshgrid(torch.arange(W, device="cuda", dtype=torch.float32),
+                              torch.arange(H, device="cuda", dtype=torch.float32), indexing="xy")
+        K, E = (torch.from_numpy(np.asarray(m, np.float32)).cuda() for m in cams[v])
+        cam = torch.linalg.inv(K) @ torch.stack([u, w, torch.ones_like(u)], -1).reshape(-1, 3).T * depth_mid
+        world = torch.linalg.inv(E) @ torch.cat([cam, torch.ones_like(cam[:1])])
+        xyzs.append(world[:3].T.reshape(H, W, 3).contiguous())
+    res["fusion_kept_fraction_view0"] = round(float(((fuse(0)[1] & 4) != 0).float().mean()), 4)
+    pixel = depth_mid / float(cams[0][0][0, 0])
+    res["pixel_footprint"] = round(pixel, 4)
+    rgb = torch.zeros(H, W, 3, device="cuda", dtype=torch.uint8)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    masks = {"all": [torch.full((H, W), 4, device="cuda", dtype=torch.uint8) for _ in range(V)],
+             "30%": [((torch.rand(H, W, device="cuda", generator=g) < 0.3).to(torch.uint8) * 4) for _ in range(V)]}
+    records = torch.empty(H * W * fusion.RECORD_BYTES, device="cuda", dtype=torch.uint8)
+    cursor = torch.zeros(1, device="cuda", dtype=torch.int64)
+    scratch = fusion.compact_cloud(masks["all"][0], xyzs[0], rgb, records, cursor)
+    for sel, ms in masks.items():
+        row = {"selected_per_view": int((ms[0] != 0).sum()),
+               "compact_ms": _event_ms(lambda: fusion.compact_cloud(ms[0], xyzs[0], rgb, records, cursor, scratch),
+                                       before=cursor.zero_)}
+        for px in (2, 8):
+            voxel = px * pixel
+            slots = fusion._voxel_slots(None, V * H * W)
+            grid = fusion.VoxelGrid(voxel, slots, "cuda")
+            keep = torch.empty(H, W, device="cuda", dtype=torch.uint8)
+            # view 0 into an empty table: the clear is part of what is timed here (one memset of the table per call)
+            first = _event_ms(lambda: (grid.clear(), grid.claim(ms[0], xyzs[0], 0, keep)), calls=5)
+            clear = _event_ms(grid.clear, calls=5)
+            grid.clear()
+            kept = []
+            for v in range(V):
+                grid.claim(ms[v], xyzs[v], v * H * W, keep)
+                kept.append(int((keep != 0).sum()))
+            grid.check()
+            occupied = grid.occupied()
+            # a later view again: its cells are all taken, as most are for the later views of a scan
+            later = _event_ms(lambda: grid.claim(ms[V - 1], xyzs[V - 1], (V - 1) * H * W, keep))
+            grid.check()
+            kept_mask = keep.clone()
+            row["voxel_%dpx" % px] = {
+                "voxel": round(voxel, 4), "slots": slots, "table_MB": round(grid.nbytes / 1e6, 1),
+                "claim_resolve_first_view_ms": round(first - clear, 4), "table_clear_ms": clear,
+                "claim_resolve_later_view_ms": later, "kept_per_view": kept, "occupied": occupied,
+                "load_factor": round(occupied / slots, 4),
+                "compact_kept_ms": _event_ms(lambda: fusion.compact_cloud(kept_mask, xyzs[0], rgb, records, cursor, scratch),
+                                             before=cursor.zero_)}
+            del grid
+        res[sel] = row
+    return res
+
+
+def thin_main(a, net, root, data, scan):
+    voxels = [None] + [float(v) for v in a.voxels.split(",")]
+    names = ["none"] + ["voxel_%g" % v for v in voxels[1:]]
+    times, counts, sizes = {k: [] for k in names}, {}, {}
+    from damvsnet_amd import scene
+    for rep in range(a.repeats + 1):  # run 0 is the warm-up of each
+        order = list(range(len(names)))
+        for i in order[rep % len(names):] + order[:rep % len(names)]:
+            ply = os.path.join(root, names[i] + ".ply")
+            kw = {} if voxels[i] is None else {"voxel": voxels[i]}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = scene.reconstruct_scene(net, data, scan, ply, nviews=a.nviews, max_h=a.H, max_w=a.W, batch=a.batch,
+                                        inputs="device", features="scene", **kw)
+            dt = time.perf_counter() - t0
+            counts[names[i]], sizes[names[i]] = n, os.path.getsize(ply)
+            if rep:
+                times[names[i]].append(round(dt, 4))
+            print("run %d %-10s %.4f s, %d points%s" % (rep, names[i], dt, n, "" if rep else " (warm-up)"), flush=True)
+    res = {"metric": "seconds, loaded model to PLY on disk, reconstruct_scene(inputs=device, features=scene)",
+           "views": a.views, "shape": [a.H, a.W], "points": counts, "ply_bytes": sizes}
+    for k in names:
+        res[k + "_s"], res[k + "_median_s"] = times[k], round(float(np.median(times[k])), 4)
+    res["launches"] = thin_launches(a, a.H, a.W)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--thin", action="store_true", help="the voxel-thinning record instead (the module docstring)")
+    ap.add_argument("--voxels", default="2,8", help="--thin: two voxel edges in world units")
     ap.add_argument("--views", type=int, default=11)
     ap.add_argument("--H", type=int, default=1184)
     ap.add_argument("--W", type=int, default=1600)
@@ -370,6 +495,14 @@ def main():
         new_w, new_h, _ = mvsio.scale_mvs_camera(H0, W0, np.eye(3, dtype=np.float32), a.W, a.H)
         resized = (new_h, new_w) != (H0, W0)
         print("scene written: %d views at %d x %d, working size %d x %d" % (a.views, H0, W0, new_h, new_w), flush=True)
+        if a.thin:
+            line = json.dumps(thin_main(a, net, root, data, scan))
+            print(line, flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+            return
         names = ("files", "memory", "device", "cached")
         times, counts = {k: [] for k in names}, {}
         read = lambda name: open(os.path.join(root, name + ".ply"), "rb").read()
