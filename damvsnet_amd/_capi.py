@@ -122,6 +122,11 @@ SIGNATURES = (
     ("damvs_fusion_cloud_scratch", c_int, (c_int, c_int)),
     ("damvs_fusion_cloud", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
                                    c_void_p, ctypes.c_longlong, c_void_p)),
+    ("damvs_fusion_normals", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(DamvsFusionCams),
+                                     ctypes.c_double, c_void_p)),
+    ("damvs_fusion_cloud_oriented", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            ctypes.POINTER(DamvsFusionCams), ctypes.c_double, c_void_p, c_void_p,
+                                            c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p)),
     ("damvs_cloud_thin_table_bytes", c_int, (ctypes.c_longlong, ctypes.POINTER(c_size_t))),
     ("damvs_cloud_thin_hash", c_int, (ctypes.c_ulonglong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong))),
     ("damvs_cloud_thin_clear", c_int, (c_void_p, c_void_p, ctypes.c_longlong)),

@@ -292,7 +292,7 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #define DAMVS_BUILD_ID "unstamped"
 #endif
 // The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so,
-// libdamvs_inputs.so, libdamvs_features.so, libdamvs_thin.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
+// libdamvs_inputs.so, libdamvs_features.so, libdamvs_thin.so, libdamvs_normals.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
   static const std::string id = [] {
     std::string s(DAMVS_BUILD_ID);
@@ -301,7 +301,8 @@ const char* damvs_build_id(void) {
                                                         {"libdamvs_scene.so", scene_build_id()},
                                                         {"libdamvs_inputs.so", inputs_build_id()},
                                                         {"libdamvs_features.so", features_build_id()},
-                                                        {"libdamvs_thin.so", thin_build_id()}};
+                                                        {"libdamvs_thin.so", thin_build_id()},
+                                                        {"libdamvs_normals.so", normals_build_id()}};
     for (const auto& l : side)
       if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
     return s;
@@ -975,6 +976,57 @@ int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, co
   a.capacity = capacity;
   a.cursor = cursor;
   return hip_check(launch_fusion_cloud(static_cast<hipStream_t>(stream), a), "fusion_cloud launch");
+}
+
+// ============================================================================ point normals
+// Validation and packing shared by the map and the scatter form.
+static int normals_pack(int H, int W, const float* depth_avg, const unsigned char* mask, const damvs_fusion_cams* cams,
+                        double jump, NormalArgs& a) {
+  if (!depth_avg || !mask || !cams) return fail(DAMVS_E_ARG, "null argument");
+  // NaN fails the first comparison, +inf the second
+  if (!(jump >= 0.0 && jump <= 1.7976931348623157e308)) return fail(DAMVS_E_ARG, "jump %g is not a finite number >= 0", jump);
+  if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return fail(DAMVS_E_SHAPE, "bad shape %d x %d", H, W);
+  std::memset(&a, 0, sizeof(a));
+  a.H = H;
+  a.W = W;
+  a.n = (long long)H * W;
+  a.ntiles = (unsigned)fusion_cloud_tiles(a.n);
+  a.depth = depth_avg;
+  a.mask = mask;
+  std::memcpy(a.kinv, cams->kinv_ref, sizeof(a.kinv));
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) a.rinv[3 * i + j] = cams->einv_ref[4 * i + j];
+  a.jump = jump;
+  return DAMVS_OK;
+}
+
+int damvs_fusion_normals(void* stream, int H, int W, const float* depth_avg, const unsigned char* mask,
+                         const damvs_fusion_cams* cams, double jump, float* normals) {
+  if (!normals) return fail(DAMVS_E_ARG, "null argument");
+  NormalArgs a;
+  DAMVS_TRY(normals_pack(H, W, depth_avg, mask, cams, jump, a));
+  a.normals = normals;
+  return hip_check(launch_normal_map(static_cast<hipStream_t>(stream), a), "fusion_normals launch");
+}
+
+int damvs_fusion_cloud_oriented(void* stream, int H, int W, const unsigned char* select, const unsigned char* mask,
+                                const float* depth_avg, const damvs_fusion_cams* cams, double jump, const float* xyz,
+                                const unsigned char* rgb, unsigned int* scratch, long long scratch_elems,
+                                unsigned char* records, long long capacity, unsigned long long* cursor) {
+  if (!select || !xyz || !rgb || !scratch || !cursor || (!records && capacity != 0)) return fail(DAMVS_E_ARG, "null argument");
+  NormalArgs a;
+  DAMVS_TRY(normals_pack(H, W, depth_avg, mask, cams, jump, a));
+  if (capacity < 0) return fail(DAMVS_E_ARG, "capacity %lld < 0", capacity);
+  // count and scan of damvs_fusion_cloud over `select` (its scatter returns at once at capacity 0): the tile offsets
+  // and the cursor's base are then in scratch, and the cursor has advanced
+  DAMVS_TRY(damvs_fusion_cloud(stream, H, W, select, xyz, rgb, scratch, scratch_elems, nullptr, 0, cursor));
+  a.select = select;
+  a.xyz = xyz;
+  a.rgb = rgb;
+  a.scratch = scratch;
+  a.records = records;
+  a.capacity = capacity;
+  return hip_check(launch_cloud_oriented(static_cast<hipStream_t>(stream), a), "fusion_cloud_oriented launch");
 }
 
 // ============================================================================ scene ingest

@@ -287,6 +287,28 @@ struct ThinArgs {
 hipError_t launch_cloud_thin(hipStream_t s, const ThinArgs& a);
 const char* thin_build_id();
 
+// ---------------------------------------------------------------- point normals (k_normals.hip, libdamvs_normals.so)
+struct NormalArgs {
+  int H, W;
+  long long n;                  // H * W
+  unsigned ntiles;              // fusion_cloud_tiles(n)
+  const float* depth;           // [n] the fusion's depth_avg
+  const unsigned char* mask;    // [n] the fusion's mask: bit value 4 (final) says which neighbours count
+  float kinv[9], rinv[9];       // inv(K_ref) and the rotation rows of inv(E_ref), as damvs_fusion_cams holds them
+  double jump;                  // relative depth step above which a neighbour is not used
+  float* normals;               // map form: [n][3]
+  // scatter form (after launch_fusion_cloud at capacity 0 with `select` as its mask, same stream and scratch)
+  const unsigned char* select;  // [n] bit value 4 selects the pixel
+  const float* xyz;             // [n][3]
+  const unsigned char* rgb;     // [n][3]
+  const unsigned* scratch;      // [ntiles + 2] as cloud_scan_kernel left it
+  unsigned char* records;       // 27-byte records
+  long long capacity;
+};
+hipError_t launch_normal_map(hipStream_t s, const NormalArgs& a);
+hipError_t launch_cloud_oriented(hipStream_t s, const NormalArgs& a);
+const char* normals_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -341,30 +341,65 @@ def _ply_header(n):
             % n).encode("ascii")
 
 
-def write_ply(filename, xyz, rgb):
+PLY_ORIENTED_RECORD_BYTES = 27  # x, y, z, nx, ny, nz float32 + red, green, blue uint8, packed
+_PLY_ORIENTED_DTYPE = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                       ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+
+
+def _ply_oriented_header(n):
+    return ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n"
+            "property float z\nproperty float nx\nproperty float ny\nproperty float nz\nproperty uchar red\n"
+            "property uchar green\nproperty uchar blue\nend_header\n" % n).encode("ascii")
+
+
+def write_ply(filename, xyz, rgb, normals=None):
     """Binary little-endian PLY of vertices (x, y, z float32; red, green, blue uint8), the element
-    layout filter/dypcd.py:306-326 writes through plyfile."""
+    layout filter/dypcd.py:306-326 writes through plyfile. normals (n, 3): the oriented layout instead, x, y, z, nx, ny,
+    nz float32 then red, green, blue (27 bytes a vertex), the property names MeshLab, Open3D and the Poisson
+    reconstruction tools read."""
     xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
     rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
-    v = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"),
-                                  ("blue", "u1")])
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if not len(nrm) == len(xyz) == len(rgb):
+            raise ValueError("%d points, %d normals, %d colours" % (len(xyz), len(nrm), len(rgb)))
+        v = np.empty(len(xyz), dtype=_PLY_ORIENTED_DTYPE)
+        v["nx"], v["ny"], v["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    else:
+        v = np.empty(len(xyz), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"),
+                                      ("blue", "u1")])
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     with open(filename, "wb") as f:
-        f.write(_ply_header(len(v)))
+        f.write(_ply_header(len(v)) if normals is None else _ply_oriented_header(len(v)))
         f.write(v.tobytes())
 
 
-def write_ply_records(filename, records_bytes):
+def write_ply_records(filename, records_bytes, normals=False):
     """write_ply's file from vertex records already packed as it packs them (15 bytes each: x, y, z little-endian
     float32, red, green, blue), e.g. the buffer fusion.compact_cloud fills: bytes, bytearray, memoryview or a uint8
-    numpy array."""
+    numpy array. normals=True: the oriented records of 27 bytes (x, y, z, nx, ny, nz, then red, green, blue)."""
     data = memoryview(records_bytes).cast("B")
-    if data.nbytes % PLY_RECORD_BYTES:
-        raise ValueError("%d bytes are not a whole number of %d-byte records" % (data.nbytes, PLY_RECORD_BYTES))
+    rec = PLY_ORIENTED_RECORD_BYTES if normals else PLY_RECORD_BYTES
+    if data.nbytes % rec:
+        raise ValueError("%d bytes are not a whole number of %d-byte records" % (data.nbytes, rec))
     with open(filename, "wb") as f:
-        f.write(_ply_header(data.nbytes // PLY_RECORD_BYTES))
+        f.write((_ply_oriented_header if normals else _ply_header)(data.nbytes // rec))
         f.write(data)
+
+
+def read_ply_oriented(filename):
+    """Inverse of write_ply(..., normals=) -> (xyz float32 (n,3), normals float32 (n,3), rgb uint8 (n,3)). ValueError
+    for a file without the nx, ny, nz properties (read_ply reads those)."""
+    with open(filename, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    if data[:end] != _ply_oriented_header(int(re.search(rb"element vertex (\d+)", data[:end]).group(1))):
+        raise ValueError("%s does not have the oriented vertex layout x y z nx ny nz red green blue" % filename)
+    n = int(re.search(rb"element vertex (\d+)", data[:end]).group(1))
+    v = np.frombuffer(data[end:], dtype=_PLY_ORIENTED_DTYPE, count=n)
+    return (np.stack([v["x"], v["y"], v["z"]], 1), np.stack([v["nx"], v["ny"], v["nz"]], 1),
+            np.stack([v["red"], v["green"], v["blue"]], 1))
 
 
 def read_ply(filename):

@@ -142,16 +142,19 @@ class SceneMaps:
                 raise ValueError("view %d %s but was added without cams" % (v, what))
 
     def fuse(self, pairs, plyfilename, conf=(0.1, 0.15, 0.9), dist_base=0.25, rel_diff_base=1 / 1300, method="dypcd",
-             thres_view=5, mask_dir=None, max_points=None, voxel=None, voxel_slots=None):
+             thres_view=5, mask_dir=None, max_points=None, voxel=None, voxel_slots=None, normals=False,
+             normal_jump=0.01):
         """fusion.fuse_scene's per-pair loop over the stores (fusion.fuse_resident): per pair the fusion kernel and
         compact_cloud on one cursor, one copy of count * 15 bytes, mvsio.write_ply_records. pairs: [(ref view,
         [source views])] or the path of a pair.txt (read as filter/dypcd.py:84-95 reads it); mask_dir: where the photo /
         geo / final PNGs go (None: not written). Positions, masks and point order are those of fuse_scene over the
         files `save` writes, bit for bit; colours too when those images are lossless (the module docstring).
         voxel, voxel_slots: thin the cloud on the device to one point per cell of a grid of that edge
-        (fusion.fuse_resident's docstring).
+        (fusion.fuse_resident's docstring). normals, normal_jump: the oriented PLY, 27 bytes a point, each normal
+        computed on the device from the view's averaged depth (fusion.fuse_resident's docstring).
         A pair that names a view never added raises ValueError and writes no PLY. Returns the point count."""
         fusion.check_voxel(voxel, voxel_slots)
+        fusion.check_normal_jump(normal_jump)
         if isinstance(pairs, (str, os.PathLike)):
             pairs = mvsio.read_pair_file(pairs)
         pairs = [(int(r), [int(s) for s in src]) for r, src in pairs]
@@ -166,7 +169,8 @@ class SceneMaps:
         confs = {v: tuple(self.conf[self.slot[v], k] for k in range(3)) for v in refs}
         rgbs = {v: self.rgb[self.slot[v]] for v in refs}
         return fusion.fuse_resident(pairs, self.cams, depths, confs, rgbs, plyfilename, conf, dist_base, rel_diff_base,
-                                    method, thres_view, mask_dir, max_points, self.depth.device, voxel, voxel_slots)
+                                    method, thres_view, mask_dir, max_points, self.depth.device, voxel, voxel_slots,
+                                    normals=normals, normal_jump=normal_jump)
 
     # ------------------------------------------------------------------------------------------------ save
     def save(self, outdir, scan, lossless=False):
@@ -424,9 +428,10 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
     between: mvsio.EvalScenes samples in batches of `batch` reference views through `model` (a CascadeMVSNet on a HIP
     device; `streams` as in its forward) with check_range=False, each batch into a SceneMaps, one
     model.DepthNet.check_range() after the last batch, then SceneMaps.fuse over the scan's pair.txt with
-    `fuse_kwargs` (conf, dist_base, rel_diff_base, method, thres_view, mask_dir, max_points, voxel, voxel_slots; the
-    last two thin the cloud to one point per voxel, fusion.fuse_resident's docstring, and a bad value raises ValueError
-    before the scan is read). Every image of the scan is
+    `fuse_kwargs` (conf, dist_base, rel_diff_base, method, thres_view, mask_dir, max_points, voxel, voxel_slots, normals,
+    normal_jump; voxel and voxel_slots thin the cloud to one point per voxel, normals=True writes the oriented PLY with a
+    normal per point, fusion.fuse_resident's docstring, and a bad value of these raises ValueError before the scan is
+    read). Every image of the scan is
     decoded and scaled once (EvalScenes' cache_views). All views must come out at one size. Returns the point count.
     Colours are taken before the reference's JPEG re-encoding (the module docstring).
     inputs: "host" converts, resizes and stacks the images with numpy and torch on the CPU and uploads every batch as
@@ -447,6 +452,7 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
     if not isinstance(decode_workers, int) or decode_workers < 1:
         raise ValueError("decode_workers must be a positive integer (got %r)" % (decode_workers,))
     fusion.check_voxel(fuse_kwargs.get("voxel"), fuse_kwargs.get("voxel_slots"))
+    fusion.check_normal_jump(fuse_kwargs.get("normal_jump", 0.01))
     ds = mvsio.EvalScenes(datapath, [scan], nviews, ndepths=ndepths, interval_scale=interval_scale, max_h=max_h,
                           max_w=max_w, cache_views=True)
     device = next(model.parameters()).device

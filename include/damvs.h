@@ -347,6 +347,40 @@ int damvs_fusion_cloud(void* stream, int H, int W, const unsigned char* mask, co
                        unsigned int* scratch, long long scratch_elems, unsigned char* records, long long capacity,
                        unsigned long long* cursor);
 
+/* ------------------------------------------------------------------ oriented cloud: per-point normals (f4)
+ * The normal of every final pixel of a fused view, from the view's averaged depth map and its camera: each point is a
+ * pixel of an organised map, so the normal is a cross product of two finite differences and its orientation towards the
+ * camera is known. fusion.normals_statement (Python) is the same rule in numpy; the kernels equal it bit for bit.
+ * Inputs: depth_avg [H][W] and mask [H][W] as damvs_fusion_view wrote them (only bit value 4, final, is read); of cams
+ * only kinv_ref (Kinv) and the rotation rows of einv_ref (Rinv) are read; jump, a relative depth step.
+ * All arithmetic is IEEE double on the float32 inputs, one rounding per operation, sums left to right, no fused
+ * multiply-add. For a final pixel c = (x, y), d = depth_avg:
+ *   P(q) = Kinv (x_q d_q, y_q d_q, d_q), the camera-frame point of pixel q;
+ *   a 4-neighbour q is usable when it lies inside the image, is final and |d_q - d_c| <= jump * d_c (NaN: not usable);
+ *   tx = P(E) - P(W) when east (x + 1) and west are usable, P(E) - P(c) or P(c) - P(W) when one is, else missing;
+ *   ty the same with south (y + 1) and north (y - 1);
+ *   n = ty x tx, negated when n . P(c) > 0 (it faces the camera), n_cam = n / sqrt(n . n);
+ *   when a tangent is missing or n . n is 0 or not finite: n_cam = -P(c) / sqrt(P(c) . P(c)), the direction to the camera;
+ *   normal = (float) Rinv n_cam, not renormalised; (0, 0, 0) when a component is not finite.
+ * damvs_fusion_normals writes normals [H][W][3] float32, (0, 0, 0) for pixels that are not final: one launch.
+ * damvs_fusion_cloud_oriented is damvs_fusion_cloud with records of 27 bytes: x, y, z, nx, ny, nz little-endian float32,
+ * then red, green, blue, packed without padding. `select` [H][W] picks the pixels (bit value 4): the fusion's mask, or
+ * damvs_cloud_thin's keep; `mask` is the fusion's mask, by which the neighbours are judged (a selected pixel that is not
+ * final there gets the normal (0, 0, 0)). The normal is computed in the scatter; no normal map is written. Order, cursor
+ * and capacity are damvs_fusion_cloud's: record i of the view goes to byte (base + i) * 27 if and only if
+ * base + i < capacity, *cursor advances by the view's count either way, capacity 0 only counts (records may be NULL).
+ * Four launches on `stream` (damvs_fusion_cloud's three at capacity 0, then the oriented scatter, which reads their
+ * scan from `scratch`), no atomics, nothing synchronised; calls that share a cursor must be enqueued on one stream.
+ * scratch: damvs_fusion_cloud_scratch(H, W) unsigned ints.
+ * Errors (before any device work): a null pointer, a jump that is negative, infinite or NaN, scratch_elems too small or
+ * capacity < 0 -> DAMVS_E_ARG; H < 1, W < 1 or H * W >= 2^31 -> DAMVS_E_SHAPE. */
+int damvs_fusion_normals(void* stream, int H, int W, const float* depth_avg, const unsigned char* mask,
+                         const damvs_fusion_cams* cams, double jump, float* normals);
+int damvs_fusion_cloud_oriented(void* stream, int H, int W, const unsigned char* select, const unsigned char* mask,
+                                const float* depth_avg, const damvs_fusion_cams* cams, double jump, const float* xyz,
+                                const unsigned char* rgb, unsigned int* scratch, long long scratch_elems,
+                                unsigned char* records, long long capacity, unsigned long long* cursor);
+
 /* ------------------------------------------------------------------ voxel-thinned cloud (f4)
  * At most one point per cell of an axis-aligned grid, chosen on the device between the fusion kernel and
  * damvs_fusion_cloud: of a scene's selected pixels (mask bit value 4), the first one in cloud order of every cell is

@@ -44,6 +44,11 @@ One JSON line, appended to --out when given.
     resolve pair, for an edge of 2 and of 8 pixel footprints (about 4 and 64 pixels per cell and view): view 0 into an
     empty table (every cell inserted) and the later views of the scan (most cells already taken), with the table's bytes
     and the load factor after all views.
+
+--normals runs the oriented-cloud record instead (fusion's normals= option, k_normals.hip) and prints its own JSON line:
+`reconstruct_scene(inputs="device", features="scene")` with and without normals=True, interleaved after one warm-up of
+each, and per view of 1184 x 1600, with the mask forced to every pixel and to a random 30 %, compact_cloud, its oriented
+form and the normal map launch, each timed alone with a record buffer that holds every call's records.
 """
 import argparse
 import ctypes
@@ -467,8 +472,75 @@ def thin_main(a, net, root, data, scan):
     return res
 
 
+def normal_launches(a, H, W, calls=20):
+    """Per reference view, each alone: compact_cloud's three launches (15-byte records), its oriented form (the same
+    three at capacity 0, then the oriented scatter: 27-byte records with the normal computed per selected pixel) and the
+    normal map launch. The record buffer holds `calls` views, so every timed call scatters all its records."""
+    from damvsnet_amd import fusion, synth
+    proj, _, dv = synth.cameras(1, a.views, H, W)
+    K, E = proj["stage3"][0, 0, 1, :3, :3].copy(), proj["stage3"][0, 0, 0].copy()
+    depth_mid = float(dv[0, 0] + dv[0, -1]) / 2
+    g = torch.Generator(device="cuda").manual_seed(0)
+    # a smooth surface with relief of a few per cent: most neighbours pass the 0.01 step test, some do not
+    yy, xx = torch.meshgrid(torch.arange(H, device="cuda", dtype=torch.float32),
+                            torch.arange(W, device="cuda", dtype=torch.float32), indexing="ij")
+    depth = (depth_mid * (1 + 0.05 * torch.sin(xx / 40) * torch.cos(yy / 55))).contiguous()
+    xyz = torch.rand(H, W, 3, device="cuda", generator=g)
+    rgb = torch.zeros(H, W, 3, device="cuda", dtype=torch.uint8)
+    masks = {"all": torch.full((H, W), 4, device="cuda", dtype=torch.uint8),
+             "30%": (torch.rand(H, W, device="cuda", generator=g) < 0.3).to(torch.uint8) * 4}
+    cams = fusion.fusion_cams(K, E, [])
+    cursor = torch.zeros(1, device="cuda", dtype=torch.int64)
+    res = {"shape": [H, W], "calls_per_block": calls}
+    for sel, m in masks.items():
+        n = int((m != 0).sum())
+        plain = torch.empty(calls * n * fusion.RECORD_BYTES, device="cuda", dtype=torch.uint8)
+        oriented = torch.empty(calls * n * fusion.ORIENTED_RECORD_BYTES, device="cuda", dtype=torch.uint8)
+        scratch = fusion.compact_cloud(m, xyz, rgb, plain, cursor)
+        row = {"selected_per_view": n,
+               "compact_ms": _event_ms(lambda: fusion.compact_cloud(m, xyz, rgb, plain, cursor, scratch), calls=calls,
+                                       before=cursor.zero_),
+               "compact_oriented_ms": _event_ms(lambda: fusion.compact_cloud(
+                   m, xyz, rgb, oriented, cursor, scratch, depth_avg=depth, cam=cams, normal_jump=0.01), calls=calls,
+                   before=cursor.zero_),
+               "normal_map_ms": _event_ms(lambda: fusion.normal_map(depth, m, K, E, 0.01), calls=calls)}
+        row["record_MB"] = {"plain": round(n * fusion.RECORD_BYTES / 1e6, 1),
+                            "oriented": round(n * fusion.ORIENTED_RECORD_BYTES / 1e6, 1)}
+        res[sel] = row
+        del plain, oriented
+    return res
+
+
+def normals_main(a, net, root, data, scan):
+    from damvsnet_amd import scene
+    names = ["plain", "normals"]
+    times, counts, sizes = {k: [] for k in names}, {}, {}
+    for rep in range(a.repeats + 1):  # run 0 is the warm-up of each
+        for name in names[rep % 2:] + names[:rep % 2]:
+            ply = os.path.join(root, name + ".ply")
+            kw = {"normals": True} if name == "normals" else {}
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = scene.reconstruct_scene(net, data, scan, ply, nviews=a.nviews, max_h=a.H, max_w=a.W, batch=a.batch,
+                                        inputs="device", features="scene", **kw)
+            dt = time.perf_counter() - t0
+            counts[name], sizes[name] = n, os.path.getsize(ply)
+            if rep:
+                times[name].append(round(dt, 4))
+            print("run %d %-8s %.4f s, %d points%s" % (rep, name, dt, n, "" if rep else " (warm-up)"), flush=True)
+    res = {"metric": "seconds, loaded model to PLY on disk, reconstruct_scene(inputs=device, features=scene)",
+           "views": a.views, "shape": [a.H, a.W], "points": counts, "ply_bytes": sizes}
+    for k in names:
+        res[k + "_s"], res[k + "_median_s"] = times[k], round(float(np.median(times[k])), 4)
+    res["launches"] = normal_launches(a, a.H, a.W)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--normals", action="store_true",
+                    help="the oriented-cloud record instead: reconstruct_scene with and without normals=True, and the "
+                         "oriented compaction beside the 15-byte one per view")
     ap.add_argument("--thin", action="store_true", help="the voxel-thinning record instead (the module docstring)")
     ap.add_argument("--voxels", default="2,8", help="--thin: two voxel edges in world units")
     ap.add_argument("--views", type=int, default=11)
@@ -495,8 +567,8 @@ def main():
         new_w, new_h, _ = mvsio.scale_mvs_camera(H0, W0, np.eye(3, dtype=np.float32), a.W, a.H)
         resized = (new_h, new_w) != (H0, W0)
         print("scene written: %d views at %d x %d, working size %d x %d" % (a.views, H0, W0, new_h, new_w), flush=True)
-        if a.thin:
-            line = json.dumps(thin_main(a, net, root, data, scan))
+        if a.thin or a.normals:
+            line = json.dumps((normals_main if a.normals else thin_main)(a, net, root, data, scan))
             print(line, flush=True)
             if a.out:
                 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
