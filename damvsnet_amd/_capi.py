@@ -58,6 +58,13 @@ class DamvsFusionCams(ctypes.Structure):
                 ("kinv_src", (_f * 9) * FUSION_MAX_SRC), ("t_rs", (_f * 16) * FUSION_MAX_SRC)]
 
 
+CONSENSUS_MAX_VIEWS = 64
+
+
+class DamvsConsensusCam(ctypes.Structure):
+    _fields_ = [("k", _f * 9), ("kinv", _f * 9), ("e", _f * 16), ("einv", _f * 16)]
+
+
 # (name, restype, argtypes) — the full exported surface of include/damvs.h
 SIGNATURES = (
     ("damvs_abi_version", c_int, ()),
@@ -127,6 +134,13 @@ SIGNATURES = (
     ("damvs_fusion_cloud_oriented", c_int, (c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                             ctypes.POINTER(DamvsFusionCams), ctypes.c_double, c_void_p, c_void_p,
                                             c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p)),
+    ("damvs_consensus_table_bytes", c_int, (c_int, ctypes.POINTER(c_size_t))),
+    ("damvs_consensus_table", c_int, (c_void_p, c_int, c_int, c_int, ctypes.POINTER(DamvsConsensusCam),
+                                      ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                      ctypes.POINTER(c_void_p), c_void_p)),
+    ("damvs_consensus_view", c_int, (c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, ctypes.POINTER(c_int),
+                                     ctypes.POINTER(ctypes.c_double), c_float, ctypes.c_double, c_int, c_void_p,
+                                     c_void_p, c_void_p)),
     ("damvs_cloud_thin_table_bytes", c_int, (ctypes.c_longlong, ctypes.POINTER(c_size_t))),
     ("damvs_cloud_thin_hash", c_int, (ctypes.c_ulonglong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong))),
     ("damvs_cloud_thin_clear", c_int, (c_void_p, c_void_p, ctypes.c_longlong)),

@@ -2,8 +2,8 @@
 
 ``python -m damvsnet_amd.build`` or ``damvsnet_amd.build.build()``. Objects are compiled in
 parallel and linked into ``damvsnet_amd/libdamvs.so`` (and ``libdamvs_fusion.so``, ``libdamvs_cloud.so``,
-``libdamvs_scene.so``, ``libdamvs_inputs.so``, ``libdamvs_features.so``, ``libdamvs_thin.so``, ``libdamvs_normals.so`` beside it,
-SIDE_LIBS_WITH_NORMALS). The library carries the sha256 of the sources,
+``libdamvs_scene.so``, ``libdamvs_inputs.so``, ``libdamvs_features.so``, ``libdamvs_thin.so``, ``libdamvs_normals.so``,
+``libdamvs_consensus.so`` beside it, SIDE_LIBS_WITH_CONSENSUS). The library carries the sha256 of the sources,
 headers and compiler flags it was built from (``damvs_build_id()``, passed as -DDAMVS_BUILD_ID); a rebuild
 is skipped only when that stamp (kept beside the library in ``libdamvs.so.build_id``) equals the hash of the
 tree, and ``_capi.load_library`` refuses an in-tree library whose embedded stamp differs from the sources
@@ -57,10 +57,15 @@ THIN_LIB = os.path.join(PKG, "libdamvs_thin.so")
 THIN_UNITS = ("k_thin.hip",)
 EVERY_SIDE_LIB = LINKED_SIDE_LIBS + ((THIN_LIB, THIN_UNITS),)
 # The point-normal kernels (map, oriented scatter), pinned by tests/isa_pins_normals.json. EVERY_SIDE_LIB stays the six
-# libraries that tests/test_thin_codeobj.py describes; SIDE_LIBS_WITH_NORMALS is what the build links and checks.
+# libraries that tests/test_thin_codeobj.py describes.
 NORMALS_LIB = os.path.join(PKG, "libdamvs_normals.so")
 NORMALS_UNITS = ("k_normals.hip",)
 SIDE_LIBS_WITH_NORMALS = EVERY_SIDE_LIB + ((NORMALS_LIB, NORMALS_UNITS),)
+# The consensus fusion kernel, pinned by tests/isa_pins_consensus.json. SIDE_LIBS_WITH_NORMALS stays the seven libraries
+# that tests/test_normals_codeobj.py describes; SIDE_LIBS_WITH_CONSENSUS is what the build links and checks.
+CONSENSUS_LIB = os.path.join(PKG, "libdamvs_consensus.so")
+CONSENSUS_UNITS = ("k_consensus.hip",)
+SIDE_LIBS_WITH_CONSENSUS = SIDE_LIBS_WITH_NORMALS + ((CONSENSUS_LIB, CONSENSUS_UNITS),)
 STAMP = LIB + ".build_id"
 OBJ = os.path.join(PKG, "build_obj")
 ARCH = os.environ.get("DAMVS_ARCH", "gfx950")
@@ -83,6 +88,8 @@ for _f in ("k_planes.hip", "k_geometry.hip", "k_regress.hip", "k_fusion.hip", "k
     FILE_FLAGS[_f] = ["-fno-slp-vectorize", "-fno-vectorize"]
 # k_normals.hip must equal fusion.normals_statement bit for bit: no multiply-add may be contracted there either.
 FILE_FLAGS["k_normals.hip"] = ["-fno-slp-vectorize", "-fno-vectorize", "-ffp-contract=off"]
+# k_consensus.hip must equal fusion.consensus_statement bit for bit in the same way.
+FILE_FLAGS["k_consensus.hip"] = ["-fno-slp-vectorize", "-fno-vectorize", "-ffp-contract=off"]
 
 
 def sources():
@@ -121,7 +128,7 @@ def stamp() -> str | None:
 
 
 def _stale(want: str) -> bool:
-    return not all(os.path.exists(p) for p in (LIB,) + tuple(lib for lib, _ in SIDE_LIBS_WITH_NORMALS)) or stamp() != want
+    return not all(os.path.exists(p) for p in (LIB,) + tuple(lib for lib, _ in SIDE_LIBS_WITH_CONSENSUS)) or stamp() != want
 
 
 def _compile(src, build_id):
@@ -150,14 +157,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
             if err.strip():
                 print("[%s]\n%s" % (os.path.basename(s), err), file=sys.stderr)
     unit = lambda o: os.path.basename(o)[:-2]
-    side_units = [u for _, units in SIDE_LIBS_WITH_NORMALS for u in units]
+    side_units = [u for _, units in SIDE_LIBS_WITH_CONSENSUS for u in units]
     # libdamvs.so finds the side libraries beside itself ($ORIGIN); the package directory it was built in follows, so
     # that a copy of libdamvs.so placed beside a replacement of one of them (tests/test_fusion_static.py
     # test_foreign_fusion_library_is_refused) still loads the others from here
     links = [(lib, [o for o in objs if unit(o) in units], ["-Wl,-soname," + os.path.basename(lib)])
-             for lib, units in SIDE_LIBS_WITH_NORMALS]
+             for lib, units in SIDE_LIBS_WITH_CONSENSUS]
     links.append((LIB, [o for o in objs if unit(o) not in side_units],
-                  [lib for lib, _ in SIDE_LIBS_WITH_NORMALS] + ["-Wl,-rpath,$ORIGIN:" + PKG]))
+                  [lib for lib, _ in SIDE_LIBS_WITH_CONSENSUS] + ["-Wl,-rpath,$ORIGIN:" + PKG]))
     for lib, members, extra in links:
         tmp = lib + ".tmp"
         cmd = [HIPCC, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", tmp] + members + extra

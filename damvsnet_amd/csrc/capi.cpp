@@ -292,7 +292,7 @@ int damvs_abi_version(void) { return DAMVS_ABI_VERSION; }
 #define DAMVS_BUILD_ID "unstamped"
 #endif
 // The stamp of this library when the libraries loaded beside it (libdamvs_fusion.so, libdamvs_cloud.so, libdamvs_scene.so,
-// libdamvs_inputs.so, libdamvs_features.so, libdamvs_thin.so, libdamvs_normals.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
+// libdamvs_inputs.so, libdamvs_features.so, libdamvs_thin.so, libdamvs_normals.so, libdamvs_consensus.so) carry the same one; otherwise theirs too, so that a loader comparing the id with the hash of the sources refuses a stale or foreign set.
 const char* damvs_build_id(void) {
   static const std::string id = [] {
     std::string s(DAMVS_BUILD_ID);
@@ -302,7 +302,8 @@ const char* damvs_build_id(void) {
                                                         {"libdamvs_inputs.so", inputs_build_id()},
                                                         {"libdamvs_features.so", features_build_id()},
                                                         {"libdamvs_thin.so", thin_build_id()},
-                                                        {"libdamvs_normals.so", normals_build_id()}};
+                                                        {"libdamvs_normals.so", normals_build_id()},
+                                                        {"libdamvs_consensus.so", consensus_build_id()}};
     for (const auto& l : side)
       if (std::strcmp(l.second, DAMVS_BUILD_ID) != 0) s += std::string(" (") + l.first + ": " + l.second + ")";
     return s;
@@ -1027,6 +1028,89 @@ int damvs_fusion_cloud_oriented(void* stream, int H, int W, const unsigned char*
   a.records = records;
   a.capacity = capacity;
   return hip_check(launch_cloud_oriented(static_cast<hipStream_t>(stream), a), "fusion_cloud_oriented launch");
+}
+
+// ============================================================================ consensus fusion
+static int consensus_shape(int H, int W, int V) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return fail(DAMVS_E_SHAPE, "bad shape %d x %d", H, W);
+  if (V < 1 || V > kConsensusMaxViews) return fail(DAMVS_E_SHAPE, "V %d not in [1, %d]", V, kConsensusMaxViews);
+  return DAMVS_OK;
+}
+
+int damvs_consensus_table_bytes(int V, size_t* bytes) {
+  if (!bytes) return fail(DAMVS_E_ARG, "null argument");
+  if (V < 1 || V > kConsensusMaxViews) return fail(DAMVS_E_SHAPE, "V %d not in [1, %d]", V, kConsensusMaxViews);
+  *bytes = (size_t)V * sizeof(ConsensusEntry);
+  return DAMVS_OK;
+}
+
+int damvs_consensus_table(void* stream, int H, int W, int V, const damvs_consensus_cam* cams, const float* const* depth,
+                          const float* const* conf, const unsigned char* const* rgb, unsigned char* const* used,
+                          void* table) {
+  if (!cams || !depth || !conf || !rgb || !used || !table) return fail(DAMVS_E_ARG, "null argument");
+  DAMVS_TRY(consensus_shape(H, W, V));
+  std::vector<ConsensusEntry> host(V);
+  for (int v = 0; v < V; ++v) {
+    if (!depth[v] || !conf[v] || !rgb[v] || !used[v]) return fail(DAMVS_E_ARG, "null map of view %d", v);
+    for (int w = 0; w < v; ++w)
+      if (used[w] == used[v]) return fail(DAMVS_E_ARG, "views %d and %d share a used map", w, v);
+    ConsensusEntry& e = host[v];
+    std::memcpy(e.k, cams[v].k, sizeof(e.k));
+    std::memcpy(e.kinv, cams[v].kinv, sizeof(e.kinv));
+    std::memcpy(e.e, cams[v].e, sizeof(e.e));
+    std::memcpy(e.einv, cams[v].einv, sizeof(e.einv));
+    e.depth = depth[v];
+    e.conf = conf[v];
+    e.rgb = rgb[v];
+    e.used = used[v];
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DAMVS_TRY(hip_check(hipMemcpyAsync(table, host.data(), host.size() * sizeof(ConsensusEntry), hipMemcpyHostToDevice, s),
+                      "consensus table upload"));
+  return hip_check(hipStreamSynchronize(s), "consensus table upload");
+}
+
+int damvs_consensus_view(void* stream, int H, int W, int V, const void* table, int ref, int nsrc, const int* src,
+                         const double* fb, float prob_thr, double disp_thr, int num_consistent, unsigned char* mask,
+                         float* xyz, unsigned char* rgb_avg) {
+  if (!table || !src || !fb || !mask || !xyz || !rgb_avg) return fail(DAMVS_E_ARG, "null argument");
+  DAMVS_TRY(consensus_shape(H, W, V));
+  if (nsrc < 1 || nsrc > kConsensusMaxViews - 1)
+    return fail(DAMVS_E_SHAPE, "nsrc %d not in [1, %d]", nsrc, kConsensusMaxViews - 1);
+  if (ref < 0 || ref >= V) return fail(DAMVS_E_SHAPE, "ref %d not in [0, %d)", ref, V);
+  for (int i = 0; i < nsrc; ++i) {
+    if (src[i] < 0 || src[i] >= V) return fail(DAMVS_E_SHAPE, "source %d not in [0, %d)", src[i], V);
+    if (src[i] == ref) return fail(DAMVS_E_ARG, "ref %d is among the sources", ref);
+    for (int j = 0; j < i; ++j)
+      if (src[j] == src[i]) return fail(DAMVS_E_ARG, "source %d is listed twice", src[i]);
+  }
+  if (num_consistent < 1) return fail(DAMVS_E_ARG, "num_consistent %d < 1", num_consistent);
+  // NaN fails the first comparison, an infinity one of the two
+  if (!(prob_thr >= -3.4028234663852886e38f && prob_thr <= 3.4028234663852886e38f))
+    return fail(DAMVS_E_ARG, "prob_thr %g is not finite", (double)prob_thr);
+  if (!(disp_thr >= -1.7976931348623157e308 && disp_thr <= 1.7976931348623157e308))
+    return fail(DAMVS_E_ARG, "disp_thr %g is not finite", disp_thr);
+  ConsensusArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.H = H;
+  a.W = W;
+  a.n = (long long)H * W;
+  a.table = static_cast<const ConsensusEntry*>(table);
+  a.ref = ref;
+  a.nsrc = nsrc;
+  a.num_consistent = num_consistent;
+  a.prob_thr = prob_thr;
+  a.disp_thr = disp_thr;
+  a.mask = mask;
+  a.xyz = xyz;
+  a.rgb_avg = rgb_avg;
+  for (int i = 0; i < nsrc; ++i) {
+    if (!(fb[i] >= -1.7976931348623157e308 && fb[i] <= 1.7976931348623157e308))
+      return fail(DAMVS_E_ARG, "fb[%d] %g is not finite", i, fb[i]);
+    a.src[i] = src[i];
+    a.fb[i] = fb[i];
+  }
+  return hip_check(launch_consensus_view(static_cast<hipStream_t>(stream), a), "consensus_view launch");
 }
 
 // ============================================================================ scene ingest

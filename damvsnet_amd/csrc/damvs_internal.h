@@ -309,6 +309,33 @@ hipError_t launch_normal_map(hipStream_t s, const NormalArgs& a);
 hipError_t launch_cloud_oriented(hipStream_t s, const NormalArgs& a);
 const char* normals_build_id();
 
+// ---------------------------------------------------------------- consensus fusion (k_consensus.hip, libdamvs_consensus.so)
+constexpr int kConsensusBlock = 256;     // reference pixels per block
+constexpr int kConsensusMaxViews = 64;   // DAMVS_CONSENSUS_MAX_VIEWS: a launch takes at most 63 sources
+// One view of the scene table in device memory (damvs_consensus_table writes it, 232 bytes a view).
+struct ConsensusEntry {
+  float k[9], kinv[9], e[16], einv[16];  // K, inv(K), E, inv(E) as float32, row-major
+  const float* depth;                    // [H][W]
+  const float* conf;                     // [H][W] final-stage confidence
+  const unsigned char* rgb;              // [H][W][3]
+  unsigned char* used;                   // [H][W] 1: the sample was merged into a point of an earlier view
+};
+struct ConsensusArgs {
+  int H, W;
+  long long n;                  // H * W
+  const ConsensusEntry* table;  // [V]
+  int ref, nsrc, num_consistent;
+  float prob_thr;
+  double disp_thr;
+  unsigned char* mask;          // [n] 1 valid | 2 geo | 4 emitted | 8 consumed on entry
+  float* xyz;                   // [n][3]
+  unsigned char* rgb_avg;       // [n][3]
+  int src[kConsensusMaxViews - 1];
+  double fb[kConsensusMaxViews - 1];  // focal length times baseline per source
+};
+hipError_t launch_consensus_view(hipStream_t s, const ConsensusArgs& a);
+const char* consensus_build_id();
+
 // ---------------------------------------------------------------- stage tail (k_regress.hip)
 // prob_mfma_kernel's A operand (pack_prob_rows, capi.cpp): 18 voxel slots x 8 channels in 5 K chunks; bf16 terms per
 // fp32 prob-conv weight (hi + lo)

@@ -7,7 +7,8 @@
   method="pcd"    the static CasMVSNet filter (filter/pcd.py): one mask per source at dist_thr pixels and rel_thr
                   relative depth (the reference's constants 1 and 0.01), a pixel kept when at least thres_view
                   sources agree (damvs_fusion_view_static).
-The third method, gipuma, needs an external CUDA binary and is out of scope.
+The third method, gipuma, hands the maps to the external fusibile binary, which the reference does not ship; METHODS
+stays these two and method="gipuma" raises. The fusibile family has its own entry points here, below.
 
 `fuse_view` is the per-view primitive (device tensors in, averaged depth / masks / world points
 out); `filter_depth` mirrors filter/dypcd.py:179-326 / filter/pcd.py:116-233 over a scene directory written by
@@ -28,6 +29,17 @@ are unchanged, so the thinned PLY is a subsequence of the unthinned one. voxel=N
 red, green, blue): each point's normal from its pixel's neighbours in the view's averaged depth map, facing the view's
 camera (`normals_statement` is the rule in numpy; k_normals.hip computes it inside compact_cloud's scatter, bit for
 bit). normals=False, the default, is the path above.
+
+Consensus fusion (`fuse_consensus_scene`, `fuse_consensus_resident`, `consensus_view`; scene.SceneMaps.fuse_consensus,
+scene.reconstruct_scene(fusion="consensus")) is the fusibile family's rule over all views of a scene: a depth sample
+merged into a point is consumed and is not emitted again from its own view, the point written is the average of the
+agreeing views' 3D points and its colour the average of their colours. `consensus_statement` is the rule in numpy, with
+the thresholds the reference passes to the binary (test_uni.py:114-116, gipuma.py:170-187); k_consensus.hip, one launch
+per reference view over a scene table in device memory (damvs_consensus_view), equals it bit for bit. It is this
+project's statement of the published algorithm; the stated difference (the disparity test compares the depth of the
+point in the source camera, not the reference pixel's own depth, with the source's depth) is in the statement's
+docstring, and parity with the binary, which is not available, is unverified. Its
+per-view outputs are the maps compact_cloud and VoxelGrid.claim take, so voxel=, max_points and normals=True compose.
 """
 from __future__ import annotations
 
@@ -558,3 +570,375 @@ def fuse_resident(pairs, cams, depths, confs, rgbs, plyfilename, conf=(0.1, 0.15
         raise ValueError("the scene's point cloud needs %d points, the record buffer holds %d" % (count, capacity))
     mvsio.write_ply_records(plyfilename, records[:count * rec_bytes].cpu().numpy(), normals=bool(normals))
     return count
+
+
+# ------------------------------------------------------------------------------------------------ consensus fusion
+CONSENSUS_MAX_VIEWS = _capi.CONSENSUS_MAX_VIEWS
+CONSENSUS_SOURCES = ("all", "pairs")
+CONSENSUS_MASKS = ((1, "valid"), (2, "geo"), (4, "final"), (8, "consumed"))
+
+
+def check_consensus(prob_threshold=0.1, disp_threshold=0.15, num_consistent=3):
+    """The consensus rule's parameters -> (prob_threshold rounded to float32, disp_threshold, num_consistent) as Python
+    numbers; ValueError unless the thresholds are finite numbers and num_consistent is an integer >= 1."""
+    num = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    with np.errstate(over="ignore"):
+        finite32 = num(prob_threshold) and bool(np.isfinite(np.float32(prob_threshold)))
+    if not (finite32 and np.isfinite(prob_threshold)):
+        raise ValueError("prob_threshold must be a finite number (got %r)" % (prob_threshold,))
+    if not (num(disp_threshold) and np.isfinite(disp_threshold)):
+        raise ValueError("disp_threshold must be a finite number (got %r)" % (disp_threshold,))
+    if not (isinstance(num_consistent, (int, np.integer)) and not isinstance(num_consistent, (bool, np.bool_))
+            and num_consistent >= 1):
+        raise ValueError("num_consistent must be an integer >= 1 (got %r)" % (num_consistent,))
+    return float(np.float32(prob_threshold)), float(disp_threshold), int(num_consistent)
+
+
+def consensus_order(pairs, sources="all"):
+    """The processing order of a scene: pairs [(ref view, [source views])] -> [(ref, [sources])], reference views in
+    pair order. sources="all" (fusibile's form): every other view that the pair list names, as a reference or as a
+    source, in ascending id; "pairs": the pair's own sources with repeats dropped, the first occurrence kept.
+    ValueError: an unknown `sources`, a reference view listed twice or among its own sources, a view without any source,
+    more than CONSENSUS_MAX_VIEWS views."""
+    if sources not in CONSENSUS_SOURCES:
+        raise ValueError("sources must be one of %s (got %r)" % (CONSENSUS_SOURCES, sources))
+    pairs = [(int(r), [int(s) for s in src]) for r, src in pairs]
+    refs = [r for r, _ in pairs]
+    for r in refs:
+        if refs.count(r) > 1:
+            raise ValueError("reference view %d is listed twice" % r)
+    views = sorted({v for r, src in pairs for v in [r] + src})
+    if len(views) > CONSENSUS_MAX_VIEWS:
+        raise ValueError("%d views: consensus fusion takes at most %d" % (len(views), CONSENSUS_MAX_VIEWS))
+    order = []
+    for r, src in pairs:
+        if sources == "all":
+            src = [v for v in views if v != r]
+        else:
+            if r in src:
+                raise ValueError("reference view %d is among its own sources" % r)
+            src = list(dict.fromkeys(src))
+        if not src:
+            raise ValueError("reference view %d has no source view" % r)
+        order.append((r, src))
+    return order
+
+
+def consensus_cam(K, E):
+    """(K, inv(K), E, inv(E)) as float32: the inverses are np.linalg.inv on float32, as fusion_cams forms them."""
+    K, E = np.asarray(K, dtype=np.float32), np.asarray(E, dtype=np.float32)
+    if K.shape != (3, 3) or E.shape != (4, 4):
+        raise ValueError("a camera is K (3, 3) and E (4, 4), got %s and %s" % (K.shape, E.shape))
+    return K, np.linalg.inv(K).astype(np.float32), E, np.linalg.inv(E).astype(np.float32)
+
+
+def consensus_fb(cam_ref, cam_src):
+    """Focal length times baseline of a (reference, source) pair, a Python float: f = K_ref[0, 0]; the camera centres
+    are the translation columns of the float32 inverses, inv(E)[:3, 3]; their distance is formed in float64,
+    sqrt(dx * dx + dy * dy + dz * dz). cam_ref, cam_src: consensus_cam's tuples."""
+    cr, cs = cam_ref[3][:3, 3].astype(np.float64), cam_src[3][:3, 3].astype(np.float64)
+    dx, dy, dz = cr[0] - cs[0], cr[1] - cs[1], cr[2] - cs[2]
+    return float(np.float64(cam_ref[0][0, 0]) * np.sqrt(dx * dx + dy * dy + dz * dz))
+
+
+def _by_view(maps):
+    return dict(maps) if isinstance(maps, dict) else dict(enumerate(maps))
+
+
+def consensus_statement(depths, confs, rgbs, cams, order, prob_threshold=0.1, disp_threshold=0.15, num_consistent=3,
+                        used=None, tally=None):
+    """The consensus fusion rule in numpy, the specification of damvs_consensus_view (k_consensus.hip equals it bit for
+    bit). It is this project's statement of the published fusibile algorithm with the thresholds the reference passes
+    to that binary (test_uni.py:114-116, gipuma.py:170-187); parity with the binary itself is unverified.
+    depths, confs (the final-stage confidence), rgbs, cams: per view id (dicts, or sequences indexed by view), maps of
+    one size H x W: float32, float32, uint8 (H, W, 3), (K (3, 3), E (4, 4)). order: [(ref, [sources])], the processing
+    order (consensus_order). used: per view (H, W) uint8 state to start from (None: all zero); it is not modified.
+    tally: a dict that receives, summed over the processed (pixel, source) pairs, how many ended as 'behind'
+    (q[2] <= 0), 'outside' the image, 'invalid' source sample, 'far' (disparity test failed) or 'agree', and of those
+    that reached the rounding how many rounded x 'up' (fraction >= 0.5) and 'down'.
+    -> one dict per entry of `order`: 'ref', 'mask' (H, W) uint8 (1 valid | 2 geo | 4 emitted | 8 consumed on entry),
+    'xyz' (H, W, 3) float32 and 'rgb' (H, W, 3) uint8 (0 where nothing is emitted), 'count' (H, W) the number n of
+    agreeing sources, and 'used': a copy of every view's state after the step.
+    A sample (v, x, y) is valid when depth is finite, depth > 0 and not (conf < float32(prob_threshold)): the
+    reference's depth_map[prob_map < prob_threshold] = 0, under which a NaN confidence stays.
+    Per reference view, per pixel (x, y) whose sample is valid and whose used[ref][y, x] is 0, d its depth:
+      X = Einv_ref (Kinv_ref (x d, y d, d));
+      for each source s in list order: q = E_s X, skipped unless q[2] > 0; u = K_s q, px = floor(u[0] / u[2] + 0.5), py
+      likewise, skipped unless both are finite and inside the image; skipped unless the sample (s, px, py) is valid, ds
+      its depth; skipped unless |fb / q[2] - fb / ds| < disp_threshold, fb = consensus_fb (focal length times baseline);
+      otherwise X_s = Einv_s (Kinv_s (px ds, py ds, ds)) is added to the position sum, rgb[s][py, px] to three integer
+      channel sums, used[s][py, px] is set to 1 (here, before the count is known, as fusibile does) and n counts it;
+      when n >= num_consistent the pixel emits (X + X_s1 + X_s2 + ...) / (n + 1), summed in list order, divided in
+      float64 and cast to float32, and per channel (2 (c_ref + sum c_s) + (n + 1)) // (2 (n + 1)).
+    fusibile compares the reference pixel's own depth with ds; the disparity test here compares the depth of X in the
+    source camera, q[2], with ds, which is the same for fronto-parallel rectified cameras and also right for rotated
+    ones.
+    Arithmetic: the fusion kernels' convention. Matrices are float32 (inverses by np.linalg.inv on float32) widened to
+    float64, every product and sum one float64 operation, the sums written out term by term in mv3 / mv34 order
+    (fusion_device.h): nothing a library may fuse or reorder.
+    Why the result does not depend on the order of the pixels: a view's pass sets bytes of other views' `used` to 1 and
+    reads `used` of its own view only, which earlier views wrote and its own pass never does (a reference view is not
+    among its sources); two pixels that agree with the same source sample both count it. The views run in list order."""
+    thr, disp, num = check_consensus(prob_threshold, disp_threshold, num_consistent)
+    thr = np.float32(thr)
+    depths, confs, rgbs, cams = _by_view(depths), _by_view(confs), _by_view(rgbs), _by_view(cams)
+    order = [(int(r), [int(s) for s in src]) for r, src in order]
+    views = sorted({v for r, src in order for v in [r] + src})
+    for r, src in order:
+        if r in src or len(set(src)) != len(src) or not src:
+            raise ValueError("view %d: the sources %s must be distinct, non-empty and without the reference view" % (r, src))
+    D = {v: np.asarray(depths[v], dtype=np.float32) for v in views}
+    C = {v: np.asarray(confs[v], dtype=np.float32) for v in views}
+    RGB = {v: np.asarray(rgbs[v], dtype=np.uint8) for v in views}
+    H, W = D[views[0]].shape
+    for v in views:
+        if D[v].shape != (H, W) or C[v].shape != (H, W) or RGB[v].shape != (H, W, 3):
+            raise ValueError("view %d: the maps of a scene must be of one size" % v)
+    cam = {v: consensus_cam(*cams[v]) for v in views}
+    m64 = {v: [m.astype(np.float64) for m in cam[v]] for v in views}
+    state = {v: (np.zeros((H, W), np.uint8) if used is None else np.array(_by_view(used)[v], dtype=np.uint8))
+             for v in views}
+    with np.errstate(all="ignore"):
+        valid = {v: np.isfinite(D[v]) & (D[v] > 0) & ~(C[v] < thr) for v in views}
+    yi, xi = np.mgrid[0:H, 0:W]
+
+    def world(v, x, y, d):
+        _, Kinv, _, Einv = m64[v]
+        a0, a1 = x * d, y * d
+        c = [Kinv[i, 0] * a0 + Kinv[i, 1] * a1 + Kinv[i, 2] * d for i in range(3)]
+        return [Einv[i, 0] * c[0] + Einv[i, 1] * c[1] + Einv[i, 2] * c[2] + Einv[i, 3] for i in range(3)]
+
+    steps = []
+    for ref, srcs in order:
+        consumed = state[ref] != 0
+        act = valid[ref] & ~consumed
+        with np.errstate(all="ignore"):
+            X = world(ref, xi.astype(np.float64), yi.astype(np.float64), D[ref].astype(np.float64))
+            S = [X[0].copy(), X[1].copy(), X[2].copy()]
+            csum = RGB[ref].astype(np.int64)
+            n = np.zeros((H, W), np.int64)
+            for s in srcs:
+                K, _, E, _ = m64[s]
+                q = [E[i, 0] * X[0] + E[i, 1] * X[1] + E[i, 2] * X[2] + E[i, 3] for i in range(3)]
+                ok = act & (q[2] > 0)
+                ends = [("behind", int((act & ~ok).sum()))]
+                u = [K[i, 0] * q[0] + K[i, 1] * q[1] + K[i, 2] * q[2] for i in range(3)]
+                fx, fy = np.floor(u[0] / u[2] + 0.5), np.floor(u[1] / u[2] + 0.5)
+                frac = u[0] / u[2] - np.floor(u[0] / u[2])
+                ends += [("up", int((ok & (frac >= 0.5)).sum())), ("down", int((ok & (frac < 0.5)).sum())),
+                         ("outside", int(ok.sum()))]
+                ok &= (fx >= 0) & (fx < W) & (fy >= 0) & (fy < H)
+                ends += [("outside", -int(ok.sum())), ("invalid", int(ok.sum()))]
+                px, py = np.where(ok, fx, 0).astype(np.int64), np.where(ok, fy, 0).astype(np.int64)
+                ok &= valid[s][py, px]
+                ends += [("invalid", -int(ok.sum())), ("far", int(ok.sum()))]
+                ds = D[s][py, px].astype(np.float64)
+                fb = consensus_fb(cam[ref], cam[s])
+                ok &= np.abs(fb / q[2] - fb / ds) < disp
+                ends += [("far", -int(ok.sum())), ("agree", int(ok.sum()))]
+                if tally is not None:
+                    for name, k in ends:
+                        tally[name] = tally.get(name, 0) + k
+                Xs = world(s, px.astype(np.float64), py.astype(np.float64), ds)
+                S = [np.where(ok, S[i] + Xs[i], S[i]) for i in range(3)]
+                csum = csum + np.where(ok[..., None], RGB[s][py, px].astype(np.int64), 0)
+                state[s][py[ok], px[ok]] = 1
+                n = n + ok
+            geo = act & (n >= num)
+            k = n + 1
+            xyz = np.stack([np.where(geo, (S[i] / k.astype(np.float64)).astype(np.float32), np.float32(0))
+                            for i in range(3)], -1).astype(np.float32)
+            rgb = np.where(geo[..., None], (2 * csum + k[..., None]) // (2 * k[..., None]), 0).astype(np.uint8)
+        mask = (valid[ref] * 1 + geo * 6 + consumed * 8).astype(np.uint8)
+        steps.append({"ref": ref, "mask": mask, "xyz": xyz, "rgb": rgb, "count": np.where(act, n, 0),
+                      "used": {v: state[v].copy() for v in views}})
+    return steps
+
+
+class ConsensusTable:
+    """One scene's table on the device (damvs_consensus_table): per view its cameras and the pointers of its depth,
+    confidence, colour and `used` maps, uploaded once. views: the view ids, slot i holding views[i]; cams: view ->
+    (K, E) host arrays; depths, confs (a tensor, or fuse_resident's tuple whose first element is the final-stage
+    confidence), rgbs: view -> CUDA tensors (H, W) float32, (H, W) float32, (H, W, 3) uint8 of one size and device.
+    `used` (V, H, W) uint8 starts at zero. ValueError, before anything is launched: no view or more than
+    CONSENSUS_MAX_VIEWS, a view listed twice, a view missing its cams, depth, conf or colour, maps of different sizes,
+    tensors that are not contiguous CUDA tensors of one device."""
+
+    def __init__(self, views, cams, depths, confs, rgbs):
+        views = [int(v) for v in views]
+        if not 1 <= len(views) <= CONSENSUS_MAX_VIEWS:
+            raise ValueError("%d views: consensus fusion takes 1 to %d" % (len(views), CONSENSUS_MAX_VIEWS))
+        if len(set(views)) != len(views):
+            raise ValueError("a view is listed twice in %s" % views)
+        for name, maps in (("cams", cams), ("depth", depths), ("conf", confs), ("colour", rgbs)):
+            for v in views:
+                if v not in maps or maps[v] is None:
+                    raise ValueError("view %d is missing its %s" % (v, name))
+        final = lambda c: c[0] if isinstance(c, (tuple, list)) else c
+        self.views, self.slot = views, {v: i for i, v in enumerate(views)}
+        self.cams = {v: consensus_cam(*cams[v]) for v in views}
+        self.depth = [depths[v] for v in views]
+        self.conf = [final(confs[v]) for v in views]
+        self.rgb = [rgbs[v] for v in views]
+        shape = tuple(self.depth[0].shape)
+        for v, d, c, r in zip(views, self.depth, self.conf, self.rgb):
+            if len(shape) != 2 or tuple(d.shape) != shape or tuple(c.shape) != shape or tuple(r.shape) != shape + (3,):
+                raise ValueError("view %d: depth %s, conf %s, colour %s; the maps of a scene must be of one size %s" % (
+                    v, tuple(d.shape), tuple(c.shape), tuple(r.shape), shape))
+        dev = self.depth[0].device
+        ok = lambda t, dt: torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous()
+        for v, d, c, r in zip(views, self.depth, self.conf, self.rgb):
+            if not (ok(d, torch.float32) and ok(c, torch.float32) and ok(r, torch.uint8)):
+                raise ValueError("view %d: consensus fusion takes contiguous CUDA tensors of one device: depth and conf "
+                                 "float32, colour uint8" % v)
+        self.H, self.W = shape
+        self.device = dev
+        V = len(views)
+        lib = _capi.load_library()
+        nbytes = ctypes.c_size_t()
+        check(lib.damvs_consensus_table_bytes(V, ctypes.byref(nbytes)))
+        self.used = torch.zeros(V, self.H, self.W, device=dev, dtype=torch.uint8)
+        self.table = torch.empty(int(nbytes.value) // 8, device=dev, dtype=torch.int64)
+        cam_arr = (_capi.DamvsConsensusCam * V)()
+        for i, v in enumerate(views):
+            for name, m in zip(("k", "kinv", "e", "einv"), self.cams[v]):
+                m = np.ascontiguousarray(m, dtype=np.float32)
+                ctypes.memmove(getattr(cam_arr[i], name), m.ctypes.data, m.size * 4)
+        ptrs = lambda ts: (ctypes.c_void_p * V)(*[t.data_ptr() for t in ts])
+        check(lib.damvs_consensus_table(_capi.stream_ptr(dev), self.H, self.W, V, cam_arr, ptrs(self.depth),
+                                        ptrs(self.conf), ptrs(self.rgb), ptrs(list(self.used)),
+                                        self.table.data_ptr()))
+
+    def used_of(self, view):
+        """The (H, W) uint8 `used` map of a view (a slice of the table's state)."""
+        return self.used[self.slot[int(view)]]
+
+
+def consensus_view(table, ref, srcs, prob_threshold=0.1, disp_threshold=0.15, num_consistent=3, out=None):
+    """One reference view of consensus_statement on the device (damvs_consensus_view, k_consensus.hip), bit for bit:
+    table: the scene's ConsensusTable; ref, srcs: view ids, 1 to 63 distinct sources without the reference view.
+    -> (mask (H, W) uint8, xyz (H, W, 3) float32, rgb_avg (H, W, 3) uint8), the shapes compact_cloud takes (out: such a
+    triple to write into). One launch on the current stream, nothing synchronised: it marks `table.used` of the sources
+    and reads that of the reference view, so the views of a scene must be enqueued in order on one stream."""
+    thr, disp, num = check_consensus(prob_threshold, disp_threshold, num_consistent)
+    ref, srcs = int(ref), [int(s) for s in srcs]
+    for v in [ref] + srcs:
+        if v not in table.slot:
+            raise ValueError("view %d is not one of the table's views %s" % (v, table.views))
+    if ref in srcs or len(set(srcs)) != len(srcs) or not 1 <= len(srcs) <= CONSENSUS_MAX_VIEWS - 1:
+        raise ValueError("view %d: 1 to %d distinct sources without the reference view (got %s)" % (
+            ref, CONSENSUS_MAX_VIEWS - 1, srcs))
+    H, W, dev, n = table.H, table.W, table.device, len(srcs)
+    if out is None:
+        out = (torch.empty(H, W, device=dev, dtype=torch.uint8), torch.empty(H, W, 3, device=dev, dtype=torch.float32),
+               torch.empty(H, W, 3, device=dev, dtype=torch.uint8))
+    mask, xyz, rgb_avg = out
+    ok = lambda t, dt, shape: t.is_cuda and t.device == dev and t.dtype == dt and t.is_contiguous() and \
+        tuple(t.shape) == shape
+    if not (ok(mask, torch.uint8, (H, W)) and ok(xyz, torch.float32, (H, W, 3)) and ok(rgb_avg, torch.uint8, (H, W, 3))):
+        raise ValueError("out must be contiguous CUDA tensors of the table's device: mask (H, W) uint8, xyz (H, W, 3) "
+                         "float32, rgb_avg (H, W, 3) uint8")
+    src = (ctypes.c_int * n)(*[table.slot[s] for s in srcs])
+    fb = (ctypes.c_double * n)(*[consensus_fb(table.cams[ref], table.cams[s]) for s in srcs])
+    check(_capi.load_library().damvs_consensus_view(_capi.stream_ptr(dev), H, W, len(table.views), table.table.data_ptr(),
+                                                    table.slot[ref], n, src, fb, thr, disp, num, mask.data_ptr(),
+                                                    xyz.data_ptr(), rgb_avg.data_ptr()))
+    return mask, xyz, rgb_avg
+
+
+def _check_consensus_driver(prob_threshold, disp_threshold, num_consistent, sources, voxel, voxel_slots, normal_jump):
+    """The consensus drivers' argument check, before anything is read, launched or written."""
+    check_consensus(prob_threshold, disp_threshold, num_consistent)
+    if sources not in CONSENSUS_SOURCES:
+        raise ValueError("sources must be one of %s (got %r)" % (CONSENSUS_SOURCES, sources))
+    check_voxel(voxel, voxel_slots)
+    check_normal_jump(normal_jump)
+
+
+def fuse_consensus_resident(pairs, cams, depths, confs, rgbs, plyfilename, prob_threshold=0.1, disp_threshold=0.15,
+                            num_consistent=3, sources="all", mask_dir=None, max_points=None, device="cuda", voxel=None,
+                            voxel_slots=None, normals=False, normal_jump=0.01):
+    """Consensus fusion of a scene whose maps are on the device (consensus_statement is the rule, its docstring states
+    the differences from fusibile; parity with that binary is unverified): a surface seen by several views is written
+    once, at the average of the agreeing views' points and colours, and the samples merged into a point are not
+    emitted again from their own views. pairs: [(ref view, [source views])]; dicts by view id of cams (K, E) host arrays,
+    depths (H, W) float32, confs (the final-stage confidence, or fuse_resident's tuple starting with it) and rgbs
+    (H, W, 3) uint8, for every view used, sources too. sources="all", fusibile's form: every other view the pair list
+    names, ascending, reference views in pair order; "pairs": the pair's own sources, repeats dropped
+    (consensus_order). prob_threshold, disp_threshold, num_consistent: test_uni.py's defaults for the binary.
+    One table upload, then per reference view consensus_view and compact_cloud on one cursor, no host synchronisation
+    between views; then the valid / geo / final / consumed PNGs (mask_dir, None: not written), one copy of the records and
+    mvsio.write_ply_records. voxel, voxel_slots, max_points, normals, normal_jump: as fuse_resident; the oriented form
+    takes the view's own depth map and the consensus mask. Returns the point count.
+    ValueError before anything is launched, and no PLY: a reference view listed twice, more than 64 views, a view
+    missing its conf or colour, bad thresholds, maps of different sizes; a cloud that does not fit max_points raises
+    after the launches and writes no PLY either."""
+    _check_consensus_driver(prob_threshold, disp_threshold, num_consistent, sources, voxel, voxel_slots, normal_jump)
+    jump = float(normal_jump)
+    order = consensus_order(pairs, sources)
+    views = sorted({v for r, src in order for v in [r] + src})
+    table = ConsensusTable(views, cams, depths, confs, rgbs)
+    rec_bytes = ORIENTED_RECORD_BYTES if normals else RECORD_BYTES
+    save_masks = mask_dir is not None
+    capacity = table.H * table.W * len(order)
+    grid = None if voxel is None else VoxelGrid(voxel, _voxel_slots(voxel_slots, max(capacity, 1)), table.device)
+    base, keep = 0, None
+    if max_points is not None:
+        capacity = max(0, min(capacity, int(max_points)))
+    records = torch.empty(capacity * rec_bytes, device=table.device, dtype=torch.uint8)
+    cursor = torch.zeros(1, device=table.device, dtype=torch.int64)
+    scratch, masks = None, []
+    for ref, srcs in order:
+        mask, xyz, rgb_avg = consensus_view(table, ref, srcs, prob_threshold, disp_threshold, num_consistent)
+        chosen = mask
+        if grid is not None:
+            chosen = keep = grid.claim(mask, xyz, base, keep)
+            base += mask.numel()
+        if normals:
+            scratch = compact_cloud(chosen, xyz, rgb_avg, records, cursor, scratch, depth_avg=depths[ref],
+                                    cam=cams[ref], fusion_mask=mask, normal_jump=jump)
+        else:
+            scratch = compact_cloud(chosen, xyz, rgb_avg, records, cursor, scratch)
+        if save_masks:
+            masks.append((ref, mask))
+    if save_masks:
+        os.makedirs(mask_dir, exist_ok=True)
+        for ref, mask in masks:
+            m = mask.cpu().numpy()
+            for bit, kind in CONSENSUS_MASKS:
+                _save_mask(os.path.join(mask_dir, "%08d_%s.png" % (ref, kind)), (m & bit) != 0)
+    if grid is not None:
+        grid.check()
+    count = int(cursor.item())
+    if count > capacity:
+        raise ValueError("the scene's point cloud needs %d points, the record buffer holds %d" % (count, capacity))
+    mvsio.write_ply_records(plyfilename, records[:count * rec_bytes].cpu().numpy(), normals=bool(normals))
+    return count
+
+
+def fuse_consensus_scene(pair_folder, scan_folder, out_folder, plyfilename, prob_threshold=0.1, disp_threshold=0.15,
+                         num_consistent=3, sources="all", device="cuda", save_masks=True, max_points=None, voxel=None,
+                         voxel_slots=None, normals=False, normal_jump=0.01):
+    """fuse_scene's files in, the same kinds of files out, fused by consensus (fuse_consensus_resident): pair.txt, and for
+    every view used, sources too, cams/%08d_cam.txt, depth_est/%08d.pfm, confidence/%08d.pfm (the final stage) and
+    images/%08d.jpg, each read and uploaded once; <out_folder>/mask/%08d_{valid,geo,final,consumed}.png (save_masks)
+    and the PLY. Returns the point count."""
+    from PIL import Image
+    _check_consensus_driver(prob_threshold, disp_threshold, num_consistent, sources, voxel, voxel_slots, normal_jump)
+    pairs = mvsio.read_pair_file(os.path.join(pair_folder, "pair.txt"))
+    order = consensus_order(pairs, sources)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    pfm = lambda kind, v: up(mvsio.read_pfm(os.path.join(out_folder, kind, "%08d.pfm" % v))[0])
+    cams, depths, confs, rgbs = {}, {}, {}, {}
+    for v in sorted({v for r, src in order for v in [r] + src}):
+        cams[v] = mvsio.read_camera_parameters(os.path.join(scan_folder, "cams", "%08d_cam.txt" % v))
+        depths[v] = pfm("depth_est", v)
+        confs[v] = pfm("confidence", v)
+        img = np.array(Image.open(os.path.join(scan_folder, "images", "%08d.jpg" % v)))
+        if img.dtype != np.uint8 or img.shape != tuple(depths[v].shape) + (3,):
+            raise ValueError("image of view %d: %s %s, expected uint8 %s" % (
+                v, img.dtype, img.shape, tuple(depths[v].shape) + (3,)))
+        rgbs[v] = up(img)
+    return fuse_consensus_resident(pairs, cams, depths, confs, rgbs, plyfilename, prob_threshold, disp_threshold,
+                                   num_consistent, sources, os.path.join(out_folder, "mask") if save_masks else None,
+                                   max_points, device, voxel, voxel_slots, normals, normal_jump)

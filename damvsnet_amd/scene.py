@@ -35,6 +35,8 @@ import torch
 from . import _capi, fusion, mvsio
 from ._capi import check
 
+_fusion = fusion  # reconstruct_scene has a parameter of the module's name
+
 
 class SceneMaps:
     """The scene-resident inputs of depth fusion for the listed views, all of one size (H, W multiples of 4):
@@ -171,6 +173,38 @@ class SceneMaps:
         return fusion.fuse_resident(pairs, self.cams, depths, confs, rgbs, plyfilename, conf, dist_base, rel_diff_base,
                                     method, thres_view, mask_dir, max_points, self.depth.device, voxel, voxel_slots,
                                     normals=normals, normal_jump=normal_jump)
+
+    def fuse_consensus(self, pairs, plyfilename, prob_threshold=0.1, disp_threshold=0.15, num_consistent=3,
+                       sources="all", mask_dir=None, max_points=None, voxel=None, voxel_slots=None, normals=False,
+                       normal_jump=0.01):
+        """Consensus fusion over the stores (fusion.fuse_consensus_resident; fusion.consensus_statement is the rule): every
+        surface point once, at the average of the agreeing views' points and colours. pairs: [(ref view, [source
+        views])] or the path of a pair.txt; sources "all": every other view the pair list names, "pairs": the pair's
+        own sources. Every view used, sources too, must have been added with cams and with colour (imgs or rgb).
+        mask_dir: where the valid / geo / final / consumed PNGs go (None: not written); the other arguments as `fuse`.
+        The PLY is that of fusion.fuse_consensus_scene over the files `save` writes, bit for bit when those images are
+        lossless. A bad argument, or a view that is missing, raises ValueError before anything is launched and writes no
+        PLY. Returns the point count."""
+        fusion._check_consensus_driver(prob_threshold, disp_threshold, num_consistent, sources, voxel, voxel_slots,
+                                       normal_jump)
+        if isinstance(pairs, (str, os.PathLike)):
+            pairs = mvsio.read_pair_file(pairs)
+        pairs = [(int(r), [int(s) for s in src]) for r, src in pairs]
+        order = fusion.consensus_order(pairs, sources)
+        for r, src in order:
+            self._require([r], "is a reference view of the pair list")
+            self._require(src, "is a source of view %d" % r)
+        used = sorted({v for r, src in order for v in [r] + src})
+        for v in used:
+            if v not in self._coloured:
+                raise ValueError("view %d was added without imgs or rgb: consensus fusion averages the colours of "
+                                 "every view it uses" % v)
+        depths = {v: self.depth[self.slot[v]] for v in used}
+        confs = {v: self.conf[self.slot[v], 0] for v in used}
+        rgbs = {v: self.rgb[self.slot[v]] for v in used}
+        return fusion.fuse_consensus_resident(pairs, self.cams, depths, confs, rgbs, plyfilename, prob_threshold,
+                                              disp_threshold, num_consistent, sources, mask_dir, max_points,
+                                              self.depth.device, voxel, voxel_slots, normals, normal_jump)
 
     # ------------------------------------------------------------------------------------------------ save
     def save(self, outdir, scan, lossless=False):
@@ -422,8 +456,13 @@ def _groups(views, n):
     return [views[i:i + n] for i in range(0, len(views), n)]
 
 
+CONSENSUS_KWARGS = ("prob_threshold", "disp_threshold", "num_consistent", "sources", "mask_dir", "max_points", "voxel",
+                    "voxel_slots", "normals", "normal_jump")
+
+
 def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192, interval_scale=1.06, max_h=1184,
-                      max_w=1600, batch=4, streams=1, inputs="host", decode_workers=4, features="batch", **fuse_kwargs):
+                      max_w=1600, batch=4, streams=1, inputs="host", decode_workers=4, features="batch", fusion="pairs",
+                      **fuse_kwargs):
     """One scan from its directory (<datapath>/<scan>/{pair.txt, cams/, images/}) to a fused PLY without the disk in
     between: mvsio.EvalScenes samples in batches of `batch` reference views through `model` (a CascadeMVSNet on a HIP
     device; `streams` as in its forward) with check_range=False, each batch into a SceneMaps, one
@@ -431,7 +470,10 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
     `fuse_kwargs` (conf, dist_base, rel_diff_base, method, thres_view, mask_dir, max_points, voxel, voxel_slots, normals,
     normal_jump; voxel and voxel_slots thin the cloud to one point per voxel, normals=True writes the oriented PLY with a
     normal per point, fusion.fuse_resident's docstring, and a bad value of these raises ValueError before the scan is
-    read). Every image of the scan is
+    read). fusion: "pairs", the default, is that path. "consensus" calls SceneMaps.fuse_consensus instead (every surface
+    point once, averaged over the agreeing views: fusion.consensus_statement); `fuse_kwargs` are then its arguments
+    (prob_threshold, disp_threshold, num_consistent, sources, mask_dir, max_points, voxel, voxel_slots, normals,
+    normal_jump), checked before the scan is read as well. Every image of the scan is
     decoded and scaled once (EvalScenes' cache_views). All views must come out at one size. Returns the point count.
     Colours are taken before the reference's JPEG re-encoding (the module docstring).
     inputs: "host" converts, resizes and stacks the images with numpy and torch on the CPU and uploads every batch as
@@ -451,8 +493,19 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
         raise ValueError("features must be \"batch\" or \"scene\" (got %r)" % (features,))
     if not isinstance(decode_workers, int) or decode_workers < 1:
         raise ValueError("decode_workers must be a positive integer (got %r)" % (decode_workers,))
-    fusion.check_voxel(fuse_kwargs.get("voxel"), fuse_kwargs.get("voxel_slots"))
-    fusion.check_normal_jump(fuse_kwargs.get("normal_jump", 0.01))
+    if fusion not in ("pairs", "consensus"):
+        raise ValueError("fusion must be \"pairs\" or \"consensus\" (got %r)" % (fusion,))
+    consensus = fusion == "consensus"
+    if consensus:
+        unknown = sorted(set(fuse_kwargs) - set(CONSENSUS_KWARGS))
+        if unknown:
+            raise ValueError("fusion=\"consensus\" takes %s, not %s" % (", ".join(CONSENSUS_KWARGS), ", ".join(unknown)))
+        _fusion._check_consensus_driver(
+            fuse_kwargs.get("prob_threshold", 0.1), fuse_kwargs.get("disp_threshold", 0.15),
+            fuse_kwargs.get("num_consistent", 3), fuse_kwargs.get("sources", "all"), fuse_kwargs.get("voxel"),
+            fuse_kwargs.get("voxel_slots"), fuse_kwargs.get("normal_jump", 0.01))
+    _fusion.check_voxel(fuse_kwargs.get("voxel"), fuse_kwargs.get("voxel_slots"))
+    _fusion.check_normal_jump(fuse_kwargs.get("normal_jump", 0.01))
     ds = mvsio.EvalScenes(datapath, [scan], nviews, ndepths=ndepths, interval_scale=interval_scale, max_h=max_h,
                           max_w=max_w, cache_views=True)
     device = next(model.parameters()).device
@@ -515,4 +568,7 @@ def reconstruct_scene(model, datapath, scan, plyfilename, nviews=5, ndepths=192,
                 out = model(imgs, proj, depth_values, ins, streams=streams, check_range=False)
             maps.add(refs[i0:i0 + len(items)], out, imgs=imgs, cams=proj_host["stage3"][:, 0])
     model.DepthNet.check_range()
-    return maps.fuse(os.path.join(datapath, scan, "pair.txt"), plyfilename, **fuse_kwargs)
+    pair_file = os.path.join(datapath, scan, "pair.txt")
+    if consensus:
+        return maps.fuse_consensus(pair_file, plyfilename, **fuse_kwargs)
+    return maps.fuse(pair_file, plyfilename, **fuse_kwargs)

@@ -381,6 +381,46 @@ int damvs_fusion_cloud_oriented(void* stream, int H, int W, const unsigned char*
                                 const unsigned char* rgb, unsigned int* scratch, long long scratch_elems,
                                 unsigned char* records, long long capacity, unsigned long long* cursor);
 
+/* ------------------------------------------------------------------ consensus fusion (f4)
+ * The fusibile family's fusion over a whole scene: a depth sample that was merged into a point is consumed and is not
+ * emitted again from its own view; the point written is the average of the agreeing views' 3D points and its colour
+ * the average of their colours. fusion.consensus_statement (Python) is the same rule in numpy; the kernel equals it bit
+ * for bit. The rule is this project's statement of the published algorithm with the thresholds the reference passes to
+ * the external binary; parity with that binary is unverified.
+ * The scene table holds, per view v of 0..V-1, its cameras and the device pointers of depth [H][W] float32, conf [H][W]
+ * float32 (the final-stage confidence), rgb [H][W][3] uint8 and used [H][W] uint8 (all zero before the first view).
+ * damvs_consensus_table_bytes gives its size; damvs_consensus_table fills `table` (device memory of that size) from the
+ * host arrays: one copy on `stream`, synchronised before it returns, so the host arrays may be freed at once.
+ * damvs_consensus_view runs one reference view, one thread per pixel, one launch:
+ *   valid(v, q): depth finite, depth > 0 and not (conf < prob_thr) (a NaN confidence stays).
+ *   A pixel p = (x, y) is skipped unless valid(ref, p) and used[ref][p] == 0. Then, in IEEE double on the float32 inputs,
+ *   one rounding per operation, sums left to right, no fused multiply-add:
+ *   X = Einv_ref (Kinv_ref (x d, y d, d)); for each source s = src[i] in list order: q = E_s X, skipped unless q.z > 0;
+ *   u = K_s q, px = floor(u.x / u.z + 0.5), py likewise, skipped unless both are finite and inside the image;
+ *   skipped unless valid(s, (px, py)), ds its depth; skipped unless |fb[i] / q.z - fb[i] / ds| < disp_thr (fb[i]: focal
+ *   length times baseline of the pair, formed by the caller). Otherwise X_s = Einv_s (Kinv_s (px ds, py ds, ds)) is
+ *   added to the position sum, rgb[s][py][px] to the channel sums, used[s][py][px] = 1 and n counts the source.
+ *   When n >= num_consistent: xyz = (float)((X + X_s1 + ...) / (n + 1)), rgb_avg = (2 sum + (n + 1)) / (2 (n + 1)) in
+ *   integers per channel; otherwise xyz and rgb_avg are 0.
+ *   mask: 1 valid | 2 n >= num_consistent | 4 emitted | 8 used[ref][p] was set on entry: the mask damvs_fusion_cloud takes.
+ * A launch writes `used` of its sources only and reads `used` of its reference view only, so its result does not depend
+ * on the order of its threads; the views of a scene must run one after another on one stream.
+ * Errors (before any device work): a null pointer, ref among the sources, a repeated source, num_consistent < 1, a
+ * threshold that is infinite or NaN -> DAMVS_E_ARG; H < 1, W < 1, H * W >= 2^31, V outside 1..DAMVS_CONSENSUS_MAX_VIEWS,
+ * nsrc outside 1..DAMVS_CONSENSUS_MAX_VIEWS - 1, ref or a source outside 0..V-1 -> DAMVS_E_SHAPE. */
+#define DAMVS_CONSENSUS_MAX_VIEWS 64
+typedef struct damvs_consensus_cam {
+  float k[9], kinv[9]; /* K and inv(K), row-major */
+  float e[16], einv[16]; /* E and inv(E), row-major */
+} damvs_consensus_cam;
+int damvs_consensus_table_bytes(int V, size_t* bytes);
+int damvs_consensus_table(void* stream, int H, int W, int V, const damvs_consensus_cam* cams, const float* const* depth,
+                          const float* const* conf, const unsigned char* const* rgb, unsigned char* const* used,
+                          void* table);
+int damvs_consensus_view(void* stream, int H, int W, int V, const void* table, int ref, int nsrc, const int* src,
+                         const double* fb, float prob_thr, double disp_thr, int num_consistent, unsigned char* mask,
+                         float* xyz, unsigned char* rgb_avg);
+
 /* ------------------------------------------------------------------ voxel-thinned cloud (f4)
  * At most one point per cell of an axis-aligned grid, chosen on the device between the fusion kernel and
  * damvs_fusion_cloud: of a scene's selected pixels (mask bit value 4), the first one in cloud order of every cell is
